@@ -2,7 +2,19 @@
 """Headline benchmark: walker-likelihoods per second of the joint X-ray + SZ
 log-posterior at a 512 x 512 map and a 500-point radial grid (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, ONE timed region of exactly K
+steps (barrier + synchronisation on both sides), the outputs of the last step written to DIR where `--dump-outputs` is
+given, and the result line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (the milliseconds one
+timed step took), `config`.  Every other measurement and check described below -- the repeated regions and their median,
+the stage passes and rooflines, the CPU baseline and the parity against it, the other routes, precisions, sizes and call
+paths -- runs with `--full` only, where each `--no-...` switch still drops its own leg.  `--regions R` (either mode)
+times R regions of K steps each and reports their median.
+
+`--dump-outputs DIR` writes what a caller of the timed path receives from its last timed step as DIR/<name>.npy:
+`logp.npy`, the log-posterior of every walker (float64; with N > 1 the gathered vector of all ranks).  Inputs are seeded:
+with the same arguments they are the same from run to run, so two builds can be compared output for output.
 
 A "step" is one evaluation of the log-posterior of every walker of the ensemble
 (what one emcee iteration costs: joxsz_funcs.py:593,600,622 -> getLikelihood
@@ -20,7 +32,7 @@ with N > 1 makes THIS process the launcher: it starts N fresh child processes
 (one per GPU) before anything touches a GPU, never initialises HIP itself,
 relays rank 0's single JSON line and exits non-zero if any rank fails.
 
-Prints ONE JSON line (rank 0).  `ms_per_step` is the MEDIAN over at least 25 timed regions of `--steps` steps each (each
+Prints ONE JSON line (rank 0).  With `--full`, `ms_per_step` is the MEDIAN over at least 25 timed regions of `--steps` steps each (each
 bracketed by barrier + synchronisation; `ms_per_step_min` / `_max`, `timed_regions`, `timed_ms_total`); beside the contract's fields:
   `roofline`            the longest kernel of the step (picked from a stage pass in the warm-up): the matrix-core kernel on its
                         algorithmic flops over its HIP-event duration against the fp64 peak, or -- when the per-walker kernel is the
@@ -284,6 +296,22 @@ def with_env(env, fn):
                 os.environ[k] = v
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs`: each array as dirname/<name>.npy in float32 or float64, at most DUMP_LIMIT_BYTES in all (of a larger
+    array a fixed, seeded sample of its elements, in index order)."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if np.asarray(a).dtype == np.float32 else np.float64)
+        if a.nbytes > budget:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 # what the kernels of a step are called and what bounds them, by form of the SZ side (jx_get_conv_layout)
 STEP_KERNELS = {
     'exact': [('prep_ms', 'jx_walker2_kernel', 'per-walker work as two lean roles in one launch: parameters, priors, grid pass (pressure, mass veto, T_SZ), h(0), conversion factors | X-ray profiles, count rates, projection, Cash sum',
@@ -312,7 +340,7 @@ def main():
     ap.add_argument('--sz-only', action='store_true')
     ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
-    ap.add_argument('--regions', type=int, default=0, help='timed regions of --steps steps each (0: at least 25, and as many as 50 ms of timed work take)')
+    ap.add_argument('--regions', type=int, default=0, help='timed regions of --steps steps each (0: one; with --full at least 25, and as many as 50 ms of timed work take)')
     ap.add_argument('--no-full-map', action='store_true', help='skip the side measurement of the full-map Abel kernel, of the stream rates and of the literal route')
     ap.add_argument('--route', choices=('map', 'operator'), default='map',
                     help="'map': profile, Abel transform and row operator per walker (the BASELINE metric); 'operator': the collapsed route (jx_set_route)")
@@ -323,7 +351,14 @@ def main():
     ap.add_argument('--no-host-pointer', action='store_true', help='skip the side measurements of jx_eval with host pointers and of jx_sample (profiling runs: keeps the trace to the timed steps)')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the strong-scaling rows of BASELINE configs[3] and configs[4]')
     ap.add_argument('--no-other-routes', action='store_true', help='skip the collapsed and legacy-contracted rows')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: repeated regions and their median, stage passes and rooflines, CPU baseline and parity, the other routes, '
+                         'precisions, sizes and call paths (each --no-... switch drops its own leg); without it: set-up, warm-up, the timed steps, the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (logp: the log-posterior of every walker) as DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_full_map = args.no_f32 = args.no_host_pointer = args.no_other_configs = args.no_other_routes = True
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # no launcher: be one.  Nothing above or below this line in this process touches a GPU.
@@ -434,7 +469,7 @@ def main():
         step()
     fence()
     gather_probe = None
-    if comm is not None and not os.environ.get('JOXSZ_BENCH_STRICT_GATHER') and not os.environ.get('JOXSZ_BENCH_OVERLAP_GATHER'):
+    if args.full and comm is not None and not os.environ.get('JOXSZ_BENCH_STRICT_GATHER') and not os.environ.get('JOXSZ_BENCH_OVERLAP_GATHER'):
         # still inside the warm-up: the same short run in both gather modes (reported; the timed regions stay strict)
         gather_probe = {}
         nprobe = max(10, min(50, args.steps))
@@ -454,16 +489,18 @@ def main():
     lay = ctx.conv_layout or {}
     form = lay.get('form')
     mixed = ctx.conv == 'custom' and args.route == 'map'
-    ctx.timing_enable(1)
-    ctx.timing_reset()
-    fence()
-    for _ in range(max(10, min(50, args.steps))):
-        step()
-    fence()
-    tm_w = ctx.timing()
-    ctx.timing_enable(False)
     kernels = STEP_KERNELS.get(form, []) if mixed else []
-    dom = max(kernels, key=lambda k: tm_w[k[0]]) if kernels else None
+    tm_w = dom = None
+    if args.full:
+        ctx.timing_enable(1)
+        ctx.timing_reset()
+        fence()
+        for _ in range(max(10, min(50, args.steps))):
+            step()
+        fence()
+        tm_w = ctx.timing()
+        ctx.timing_enable(False)
+        dom = max(kernels, key=lambda k: tm_w[k[0]]) if kernels else None
     # Timed regions: `--steps` steps each, bracketed by barrier + synchronisation on both sides, at least 25 of them and at least 50 ms in
     # all; the MEDIAN region is the figure (a single 2 ms region has no spread estimate).  Inside them: the two HIP
     # events around the longest kernel of the step only (what `roofline` prices); events behind every kernel cost a few per cent of a
@@ -471,10 +508,15 @@ def main():
     p1_mode = TIMING_MODE_OF_STAGE.get(dom[0], 2) if (dom and form == 'exact') else (2 if mixed else 1)
     ctx.timing_enable(False)
     fence()
-    est = max(1e-6, tm_w['total_ms'] / max(1, tm_w['launches']) * 1e-3 * (W / max(1.0, tm_w['walkers'] / max(1, tm_w['launches']))) * args.steps)
-    if comm is not None:
-        est = comm.max_over_ranks(est)                       # (every rank runs the same number of regions: each carries a barrier)
-    nreg = args.regions if args.regions > 0 else int(min(2000, max(25, np.ceil(0.05 / est))))
+    if args.regions > 0:
+        nreg = args.regions
+    elif args.full:
+        est = max(1e-6, tm_w['total_ms'] / max(1, tm_w['launches']) * 1e-3 * (W / max(1.0, tm_w['walkers'] / max(1, tm_w['launches']))) * args.steps)
+        if comm is not None:
+            est = comm.max_over_ranks(est)                   # (every rank runs the same number of regions: each carries a barrier)
+        nreg = int(min(2000, max(25, np.ceil(0.05 / est))))
+    else:
+        nreg = 1                                             # a plain run: `--steps` timed steps, no more
     regions = []
     for _ in range(nreg):
         fence()
@@ -485,35 +527,9 @@ def main():
         regions.append(time.perf_counter() - t_start)
     if comm is not None:
         regions = [float(v) for v in comm.max_over_ranks(regions)]
-    # the same regions once more with the two HIP events around the longest kernel of the step (a pair of events between dependent
-    # kernels costs the step 3-6 us of command-processor work: the headline regions above carry none)
-    ctx.timing_enable(p1_mode)
-    ctx.timing_reset()
-    regions_ev = []
-    for _ in range(max(5, min(nreg, 25))):
-        fence()
-        t_start = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        regions_ev.append(time.perf_counter() - t_start)
-    if comm is not None:
-        regions_ev = [float(v) for v in comm.max_over_ranks(regions_ev)]
-    tm_timed = ctx.timing()
-    ctx.timing_enable(1)
-    ctx.timing_reset()
-    fence()
-    for _ in range(args.steps):
-        step()
-    fence()
-    tm = ctx.timing()
-    gather_ms = None
-    if comm is not None:
-        gms, gn = ctx.comm_gather_time()                     # the all-gathers' own durations (events on their stream) of the stage pass
-        gather_ms = gms / max(1, gn)
-    ctx.timing_enable(False)
     elapsed = float(np.median(regions))
 
+    # what the last timed step handed to its caller
     last = (nstep[0] - 1) % len(lp_ptrs)
     if comm is not None:
         final = np.empty(W * world)
@@ -524,6 +540,36 @@ def main():
     if not np.all(np.isfinite(final)):
         raise SystemExit('bench: non-finite log-probabilities in the timed batch')
     lp_own = final[rank * W:(rank + 1) * W] if comm is not None else final
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'logp': final})
+
+    regions_ev, tm_timed, tm, gather_ms = [], None, None, None
+    if args.full:
+        # the same regions once more with the two HIP events around the longest kernel of the step (a pair of events between dependent
+        # kernels costs the step 3-6 us of command-processor work: the headline regions above carry none)
+        ctx.timing_enable(p1_mode)
+        ctx.timing_reset()
+        for _ in range(max(5, min(nreg, 25))):
+            fence()
+            t_start = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            fence()
+            regions_ev.append(time.perf_counter() - t_start)
+        if comm is not None:
+            regions_ev = [float(v) for v in comm.max_over_ranks(regions_ev)]
+        tm_timed = ctx.timing()
+        ctx.timing_enable(1)
+        ctx.timing_reset()
+        fence()
+        for _ in range(args.steps):
+            step()
+        fence()
+        tm = ctx.timing()
+        if comm is not None:
+            gms, gn = ctx.comm_gather_time()                 # the all-gathers' own durations (events on their stream) of the stage pass
+            gather_ms = gms / max(1, gn)
+        ctx.timing_enable(False)
     # ---- every figure of the headline is fixed from here on; nothing below can change or lose it.  The side measurements run
     #      rank-locally inside try/except WITHOUT collectives; the ranks meet once more, in one all-reduce outside any
     #      exception handler, to agree on the strong-scaling rows (a rank that failed contributes +inf).
@@ -762,8 +808,44 @@ def main():
                 else:
                     other[key] = {'error': 'not measured on every rank'}
 
+    head = None
     if rank == 0:
+        # the headline and the configuration it was measured at: the whole line of a plain run, the front of a --full one
         S = args.S
+        value = W * world * args.steps / elapsed
+        ms_step = 1e3 * elapsed / args.steps
+        prn = ctx.output_pruning
+        none_or = lambda d, active: ({k: v for k, v in d.items() if k != 'rows'} if active else 'none')
+        tr = ctx.truncation
+        head = {
+            'metric': 'walker-likelihoods/sec at 512^2 map, 500-pt grid' if (S, args.N) == (512, 500)
+                      else 'walker-likelihoods/sec at %d^2 map, %d-pt grid' % (S, args.N),
+            'value': value, 'unit': 'walker-likelihoods/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': ms_step, 'ms_per_step_min': 1e3 * min(regions) / args.steps, 'ms_per_step_max': 1e3 * max(regions) / args.steps,
+            'timed_regions': len(regions), 'timed_ms_total': 1e3 * sum(regions),
+            'ms_per_step_note': ('median over the timed regions of `steps` steps each (every region bracketed by barrier + synchronisation; value = walkers x steps / median region; '
+                                 'no HIP event inside them: `roofline.launch_ms` comes from the same regions run once more with two events around the longest kernel)'
+                                 if len(regions) > 1 else
+                                 'one timed region of `steps` steps behind `warmup` steps, bracketed by barrier + synchronisation; value = walkers x steps / region; no HIP event inside it'),
+            'higher_is_better': True,
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic', 'full': bool(args.full),
+            'outputs_dumped_to': args.dump_outputs,
+            'config': {'workload': '%d walkers/GPU, %dx%d SZ map, %d-pt radial grid, %s likelihood, '
+                                   'synthetic CL J1226.9+3332-shaped inputs%s'
+                                   % (W, S, S, args.N, 'SZ-only' if pb.sz_only else 'joint X-ray+SZ',
+                                      ' (BASELINE configs[2])' if (W, S, args.N, pb.sz_only) == (1024, 512, 500, False) else ''),
+                       'walkers_per_gpu': W, 'S': S, 'N': args.N, 'B': pb.B, 'chunk': ctx.chunk, 'route': ctx.route, 'conv': ctx.conv, 'form': form,
+                       'conv_layout': ctx.conv_layout, 'output_pruning': prn,
+                       'sampling': none_or(ctx.sampling, ctx.sampling['active']), 'radial_sampling': none_or(ctx.radial_sampling, ctx.radial_sampling['active']),
+                       'truncation': ('none' if (tr['rank'] == 0 and tr['est_rel_row_err'] < 0) else {k: v for k, v in tr.items() if k != 'warning'}),
+                       'parallelism': 'walkers sharded x%d' % world, 'device': ctx.device_name,
+                       'gather': (('overlapped: second stream, two output buffers' if overlap else 'strict: on the compute stream, in order') if comm is not None else None),
+                       'gather_probe_ms_per_step': gather_probe},
+            'n_ranks_seen': (comm.n_ranks_seen if comm is not None else 1),
+        }
+        if not args.full:
+            print(json.dumps(head))
+    if rank == 0 and args.full:
         launches = max(1, tm['launches'])
         walkers_per_launch = tm['walkers'] / launches
         stage_keys = ('prep_ms', 'abel_map_ms', 'beam_fft_ms', 'tf_fft_ms', 'tail_ms')
@@ -772,11 +854,8 @@ def main():
             ev_null_ms = ctx.event_bracket_time(64)
         except Exception:
             ev_null_ms = None
-        value = W * world * args.steps / elapsed
-        ms_step = 1e3 * elapsed / args.steps
         pj = pmc_file(S)
         nrow = ctx.nrow
-        prn = ctx.output_pruning
         sq = sq_counters_file()
 
         def wave_shares(kernel):
@@ -842,30 +921,8 @@ def main():
                 r_['ms_per_step_of_the_default_route_over_this'] = ms_step / r_['ms_per_step']
         if ns_route and 'ms_per_step' in ns_route:
             ns_route['speedup_of_default_route'] = ns_route['ms_per_step'] / ms_step
-        none_or = lambda d, active: ({k: v for k, v in d.items() if k != 'rows'} if active else 'none')
-        tr = ctx.truncation
-        out = {
-            'metric': 'walker-likelihoods/sec at 512^2 map, 500-pt grid' if (S, args.N) == (512, 500)
-                      else 'walker-likelihoods/sec at %d^2 map, %d-pt grid' % (S, args.N),
-            'value': value, 'unit': 'walker-likelihoods/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': ms_step, 'ms_per_step_min': 1e3 * min(regions) / args.steps, 'ms_per_step_max': 1e3 * max(regions) / args.steps,
-            'timed_regions': len(regions), 'timed_ms_total': 1e3 * sum(regions),
-            'ms_per_step_note': 'median over the timed regions of `steps` steps each (every region bracketed by barrier + synchronisation; value = walkers x steps / median region; '
-                                'no HIP event inside them: `roofline.launch_ms` comes from the same regions run once more with two events around the longest kernel)',
-            'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
-            'config': {'workload': '%d walkers/GPU, %dx%d SZ map, %d-pt radial grid, %s likelihood, '
-                                   'synthetic CL J1226.9+3332-shaped inputs%s'
-                                   % (W, S, S, args.N, 'SZ-only' if pb.sz_only else 'joint X-ray+SZ',
-                                      ' (BASELINE configs[2])' if (W, S, args.N, pb.sz_only) == (1024, 512, 500, False) else ''),
-                       'walkers_per_gpu': W, 'S': S, 'N': args.N, 'B': pb.B, 'chunk': ctx.chunk, 'route': ctx.route, 'conv': ctx.conv, 'form': form,
-                       'conv_layout': ctx.conv_layout, 'output_pruning': prn,
-                       'sampling': none_or(ctx.sampling, ctx.sampling['active']), 'radial_sampling': none_or(ctx.radial_sampling, ctx.radial_sampling['active']),
-                       'truncation': ('none' if (tr['rank'] == 0 and tr['est_rel_row_err'] < 0) else {k: v for k, v in tr.items() if k != 'warning'}),
-                       'parallelism': 'walkers sharded x%d' % world, 'device': ctx.device_name,
-                       'gather': (('overlapped: second stream, two output buffers' if overlap else 'strict: on the compute stream, in order') if comm is not None else None),
-                       'gather_probe_ms_per_step': gather_probe},
-            'n_ranks_seen': (comm.n_ranks_seen if comm is not None else 1),
+        out = dict(head)
+        out.update({
             'gather_ms_per_step': gather_ms,
             'roofline': roof,
             # the whole step against the HBM roofline: measured bytes (rocprofv3 PMC, profiles/*_pmc_traffic.json)
@@ -892,7 +949,7 @@ def main():
             'stage_ms_note': 'HIP events behind every kernel, from one more pass of `steps` steps right after the timed regions',
             'parity_max_rel_err': parity,
             'other_configs': other,
-        }
+        })
         print(json.dumps(out))
     if comm is not None:
         comm.close()

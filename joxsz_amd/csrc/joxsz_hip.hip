@@ -295,7 +295,12 @@ static int dev_new_l(jx_ctx* ctx, std::vector<void*>& list, size_t count, T** ou
     HIPCHK(ctx, hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
     list.push_back(p);
     ctx->device_bytes += (int64_t)(count * sizeof(T));
-    if (zero) HIPCHK(ctx, hipMemset(p, 0, count * sizeof(T)));
+    if (zero) {
+        // hipMemset of device memory returns before the fill has run, on the null stream; the context's streams are non-blocking
+        // and do not wait for it.  Finish it here: the first writer of the buffer may be the very next call on one of them.
+        HIPCHK(ctx, hipMemset(p, 0, count * sizeof(T)));
+        HIPCHK(ctx, hipStreamSynchronize(nullptr));
+    }
     *out = (T*)p;
     return JX_OK;
 }

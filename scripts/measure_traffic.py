@@ -20,6 +20,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, os.environ.get('JOXSZ_PROFILE_OUT', 'profile_out'))     # (the folder the profiling scripts share)
+os.makedirs(OUT, exist_ok=True)
 
 
 LITERAL = len(sys.argv) > 2 and sys.argv[2] == 'literal'
@@ -29,7 +31,7 @@ def collect(counter, outdir):
     subprocess.run(['rm', '-rf', outdir])
     cmd = ['rocprofv3', '--kernel-trace', '--pmc', counter, '--output-format', 'csv', '-d', outdir, '--']
     if LITERAL: cmd += [sys.executable, os.path.join(ROOT, 'scripts', 'literal_prof.py'), '512', '500', '1024', '3']
-    else: cmd += [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu', '--no-f32', '--no-other-configs', '--no-other-routes', '--no-host-pointer', '--regions', '2']
+    else: cmd += [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '3', '--warmup', '1', '--no-cpu', '--no-f32', '--no-other-configs', '--no-other-routes', '--no-host-pointer', '--regions', '2']
     env = dict(os.environ, TMPDIR='/tmp')
     res = subprocess.run(cmd, check=True, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
     collect.bench = {'config': {'S': 512, 'N': 500, 'chunk': 1024, 'conv': 'rocfft'}} if LITERAL else json.loads(res.stdout.strip().splitlines()[-1])
@@ -48,12 +50,12 @@ def collect(counter, outdir):
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else 'r03'
-    scratch = os.path.join(ROOT, 'gpurun_out', 'traffic_' + tag)
+    scratch = os.path.join(OUT, 'traffic_' + tag)
     fetch = collect('FETCH_SIZE', scratch + '_fetch')
     write = collect('WRITE_SIZE', scratch + '_write')
     cfg = collect.bench['config']
     out = {'unit': 'bytes per launch', 'S': cfg['S'], 'N': cfg['N'], 'walkers_per_launch': cfg['chunk'], 'conv': cfg['conv'],
-           'command': 'rocprofv3 --kernel-trace --pmc <FETCH_SIZE|WRITE_SIZE> -- python3 ' + ('scripts/literal_prof.py 512 500 1024 3' if LITERAL else 'bench.py --steps 3 --warmup 1 --no-cpu --no-f32 --no-other-configs'), 'note': 'FETCH_SIZE KiB x 1024 x 2 (gfx950 wide-read correction), WRITE_SIZE KiB x 1024',
+           'command': 'rocprofv3 --kernel-trace --pmc <FETCH_SIZE|WRITE_SIZE> -- python3 ' + ('scripts/literal_prof.py 512 500 1024 3' if LITERAL else 'bench.py --full --steps 3 --warmup 1 --no-cpu --no-f32 --no-other-configs'), 'note': 'FETCH_SIZE KiB x 1024 x 2 (gfx950 wide-read correction), WRITE_SIZE KiB x 1024',
            'kernels': {}}
     for k in sorted(set(fetch) | set(write)):
         rd = fetch.get(k, 0.0) * 1024 * 2
@@ -65,7 +67,7 @@ def main():
         out['total_bytes'] = sum(v['total_bytes'] for v in out['kernels'].values())
         out['survey_8d_bytes'] = 16.0 * 512 * 512 * 1024
         out['total_over_survey_8d_bytes'] = out['total_bytes'] / out['survey_8d_bytes']
-    path = os.path.join(ROOT, 'gpurun_out', '%s_pmc_traffic%s.json' % (tag, '_literal' if LITERAL else ''))
+    path = os.path.join(OUT, '%s_pmc_traffic%s.json' % (tag, '_literal' if LITERAL else ''))
     json.dump(out, open(path, 'w'), indent=1)
     print(json.dumps(out, indent=1))
 

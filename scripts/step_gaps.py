@@ -3,8 +3,10 @@
 steady-state step.   python scripts/step_gaps.py   (on the GPU box, from the repo root)"""
 import csv, glob, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = os.path.join(ROOT, 'gpurun_out', 'gaps')
-subprocess.run(['rocprofv3', '--kernel-trace', '--output-format', 'csv', '-d', out, '--', sys.executable, os.path.join(ROOT, 'bench.py'),
+OUT = os.path.join(ROOT, os.environ.get('JOXSZ_PROFILE_OUT', 'profile_out'))     # (the folder the profiling scripts share)
+os.makedirs(OUT, exist_ok=True)
+out = os.path.join(OUT, 'gaps')
+subprocess.run(['rocprofv3', '--kernel-trace', '--output-format', 'csv', '-d', out, '--', sys.executable, os.path.join(ROOT, 'bench.py'), '--full',
                 '--steps', '20', '--warmup', '5', '--no-cpu', '--no-full-map', '--no-f32', '--no-other-configs', '--no-other-routes', '--no-host-pointer', '--regions', '2'], check=True, env=dict(os.environ, TMPDIR='/tmp'),
                stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 f = sorted(glob.glob(out + '/*/*kernel_trace.csv'))[-1]

@@ -73,10 +73,7 @@ def test_cosmology_plate_scale():
 
 
 def test_fits_reader_matches_reference_columns():
-    ref = '/root/reference/data/SZ/Beam150GHz.fits'
-    if not os.path.exists(ref):
-        import pytest
-        pytest.skip('reference data not present on this box')
+    ref = os.path.join(GOLDEN, 'Beam150GHz.fits')               # the reference's bundled beam file (data/SZ), stored as a fixture
     z = _inputs()
     r, b = sh.clip_beam_profile(*sh.read_columns(ref, 2))
     np.testing.assert_array_equal(r, z['beam_r'])
