@@ -85,6 +85,10 @@ struct MixBack {
     double *x_Wfk = nullptr;           // odd number of ordinate tiles: the last one's share of the row as an operator on the profile (timed path; jxt::exact_fold_layout)
     double *x_Typ = nullptr, *x_Opk = nullptr, *x_y = nullptr, *x_cf = nullptr, *x_P = nullptr, *x_ppi = nullptr;
     bool x_pairwise = true;            // JOXSZ_X_PAIRWISE=0: the ordinates read back by one block per 16 walkers (jx_rowop_tail_kernel)
+    bool x_contract = true;            // JOXSZ_X_CONTRACT=0: the pair-wise kernels exchange partial rows in every call (with it: only in calls with row / brightness taps)
+    bool x_ct_ok = false;              // the contracted epilogue fits this problem (LDS at three blocks per compute unit, fewer data radii than outputs)
+    int x_ldm = 0, x_ldr = 0, x_lde = 0, x_o_z = 0, x_o_E = 0, x_last_ct = -1;   // its geometry (JxRowOp); form of the last launch (-1: none yet)
+    double *x_Pm = nullptr, *x_Ec = nullptr;   // contracted partials [tW / 16][x_npair][16][x_ldm]; data-radii matrix [nflux][x_lde], the outputs in use
     JxMix mx{};
     JxOpg og{};
     JxOpg og_u{};                      // the product restricted to the outputs the tail reads (nxt_u tiles per block, ksplit_u slices); og: every output (taps)
@@ -319,7 +323,7 @@ static std::vector<T> host_vec(jx_ctx* ctx, int id) {
 // SAMPLE_ ones), with the process environment as the default of each.  The list is the one include/joxsz_hip.h documents
 // (tests/test_abi.py holds the two and the uses in this file together).
 static const char* const kOptions[] = {
-    "JOXSZ_CONV", "JOXSZ_MIX_FORM", "JOXSZ_X_PAIRWISE", "JOXSZ_X_FOLD", "JOXSZ_PRUNE_OUTPUTS", "JOXSZ_CHUNK", "JOXSZ_FFT_PAD", "JOXSZ_FFT_COLUMNS", "JOXSZ_FFT_ROWS", "JOXSZ_MAP_SPLIT", "JOXSZ_MAP_PAIR",
+    "JOXSZ_CONV", "JOXSZ_MIX_FORM", "JOXSZ_X_PAIRWISE", "JOXSZ_X_CONTRACT", "JOXSZ_X_FOLD", "JOXSZ_PRUNE_OUTPUTS", "JOXSZ_CHUNK", "JOXSZ_FFT_PAD", "JOXSZ_FFT_COLUMNS", "JOXSZ_FFT_ROWS", "JOXSZ_MAP_SPLIT", "JOXSZ_MAP_PAIR",
     "JOXSZ_EVAL_DIRECT", "JOXSZ_PREP_SPLIT", "JOXSZ_PREP_LEAN", "JOXSZ_PREP_POW", "JOXSZ_PREP_FASTMATH", "JOXSZ_OP_NARROW", "JOXSZ_SAMPLE_FUSED", "JOXSZ_SAMPLE_VIRTUAL_RANKS",
     // the contracted forms of rounds 3-4 (JOXSZ_MIX_FORM=legacy|lowrank|full)
     "JOXSZ_LOWRANK_TOL", "JOXSZ_TRUNC_PROBE", "JOXSZ_TRUNC_BOUND", "JOXSZ_MIX_SUBSAMPLE", "JOXSZ_MIX_RANKCAP", "JOXSZ_MIX_MFMA", "JOXSZ_MIX_USPLIT", "JOXSZ_MIX_WPB",
@@ -981,6 +985,24 @@ static int mix_setup(jx_ctx* ctx, const MixBuild& mb, long long tW) {
         if ((rc = dev_put_l(ctx, m.allocs, mb.xOpk.data(), mb.xOpk.size(), &m.x_Opk))) return rc;
         if ((rc = dev_new_l(ctx, m.allocs, (size_t)tW * m.Nkp, &m.x_y, true))) return rc;
         if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.x_npair * m.x_ng * 256 * m.x_nxt, &m.x_P, true))) return rc;
+        {
+            // contracted form of the pair-wise kernels: the epilogue's LDS behind the ordinate product's, three blocks per compute unit resident
+            const int nflux = ctx->d.nflux, nrow = ctx->nrow, nuse = std::min(ctx->prune ? ctx->nrow_use : nrow, nrow);
+            m.x_ldr = (nuse + 1) | 1; m.x_lde = m.x_ldr; m.x_ldm = nflux;
+            m.x_o_z = std::max(JX_ORD_LDS_DOUBLES, 16 * m.x_ldr);
+            m.x_o_E = m.x_o_z + 4 * 16 * (nflux + 1);
+            const size_t lds_ct = (size_t)52 * 1024;
+            if (sizeof(double) * ((size_t)m.x_o_E + (size_t)nflux * m.x_lde) > lds_ct) m.x_lde = 0;     // (the data-radii matrix through the caches then)
+            m.x_ct_ok = sizeof(double) * ((size_t)m.x_o_E + (size_t)nflux * m.x_lde) <= lds_ct && nflux < 16 * m.x_nxt * m.x_ng_use;
+            m.x_Pm = nullptr; m.x_Ec = nullptr; m.x_last_ct = -1;
+            if (m.x_ct_ok) {
+                if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.x_npair * 16 * m.x_ldm, &m.x_Pm, true))) return rc;
+                if (m.x_lde) {
+                    if ((rc = dev_new_l(ctx, m.allocs, (size_t)nflux * m.x_lde, &m.x_Ec, true))) return rc;
+                    HIPCHK(ctx, hipMemcpy2D(m.x_Ec, sizeof(double) * m.x_lde, ctx->d.emat, sizeof(double) * nrow, sizeof(double) * nuse, nflux, hipMemcpyDeviceToDevice));
+                }
+            }
+        }
         m.bytes = ctx->device_bytes - before;
         m.ready = true;
         return JX_OK;
@@ -1455,6 +1477,7 @@ static int finalize_impl(jx_ctx* ctx) {
     if (const char* e = opt_str(ctx, "JOXSZ_AG_NARROW")) ctx->ag_narrow = atoi(e) != 0;
     if (const char* e = opt_str(ctx, "JOXSZ_AG_SINGLE")) ctx->ag_single = atoi(e) != 0;
     if (const char* e = opt_str(ctx, "JOXSZ_X_PAIRWISE")) ctx->mix.x_pairwise = atoi(e) != 0;
+    if (const char* e = opt_str(ctx, "JOXSZ_X_CONTRACT")) ctx->mix.x_contract = atoi(e) != 0;
     if (const char* e = opt_str(ctx, "JOXSZ_PREP_SPLIT")) ctx->prep_split = atoi(e) != 0;
     if (const char* e = opt_str(ctx, "JOXSZ_PREP_LEAN")) ctx->prep_lean = atoi(e) != 0;
     if (const char* e = opt_str(ctx, "JOXSZ_AG_SUBSAMPLE")) {
@@ -2104,15 +2127,27 @@ static int run_chunk(jx_ctx* ctx, const double* theta_dev, double* logp_dev, int
             ro.Opk = m.x_Opk; ro.Typ = m.x_Typ; ro.pp = pp_src; ro.y = lean ? (double*)nullptr : m.x_y; ro.P = m.x_P;      // (lean: the ordinates stay in LDS)
             const size_t lds_max = (size_t)158 * 1024;
             const bool pairwise = m.x_pairwise;
+            // contracted form: every call of the pair-wise kernels without row / brightness taps, whatever the fold and the ordinates do (a
+            // walker's bits must not depend on them); where it does not fit, or is switched off, the partial rows as before
+            const bool contract = pairwise && m.x_contract && m.x_ct_ok && !all;
+            if (contract) {
+                ro.nflux = d.nflux; ro.nrow = d.nrow; ro.ldm = m.x_ldm; ro.ldr = m.x_ldr; ro.lde = m.x_lde;
+                ro.o_z = m.x_o_z; ro.o_E = m.x_o_E;
+                ro.cfac = ctx->d_cfac; ro.emat = d.emat; ro.Ec = m.x_Ec; ro.Pm = m.x_Pm;
+            }
+            m.x_last_ct = contract ? 1 : 0;
             {
                 JxRowOp r1 = ro;
                 if (!pairwise) r1.ng = 0;                        // (the ordinates alone: the row product reads them back)
                 const int ntw = (n + 15) / 16;
                 const dim3 grid((unsigned)(8 * ((ntw + 7) / 8) * r1.npair));
-                const size_t sh1 = sizeof(double) * JX_ORD_LDS_DOUBLES;
+                const size_t sh1 = sizeof(double) * (contract ? (size_t)ro.o_E + (size_t)ro.nflux * ro.lde : (size_t)JX_ORD_LDS_DOUBLES);
                 if (tm2 && es.p1stage == 2) HIPCHK(ctx, hipEventRecord(es.e[2], st));
                 bool done = false;
-#define JX_ORD_GO(Xv) if (!done && m.x_nxt == Xv) { hipLaunchKernelGGL((jx_ordrow_kernel<Xv>), grid, dim3(256), sh1, st, r1); done = true; }
+#define JX_ORD_GO(Xv) if (!done && m.x_nxt == Xv) { \
+                    if (contract) hipLaunchKernelGGL((jx_ordrow_kernel<Xv, true>), grid, dim3(256), sh1, st, r1); \
+                    else hipLaunchKernelGGL((jx_ordrow_kernel<Xv>), grid, dim3(256), sh1, st, r1); \
+                    done = true; }
                 JX_MIX_NXTS(JX_ORD_GO)
 #undef JX_ORD_GO
                 if (!done) { ctx->err = "no ordinate-product kernel for this output tiling"; return JX_ERR_UNSUPPORTED; }
@@ -2136,7 +2171,17 @@ static int run_chunk(jx_ctx* ctx, const double* theta_dev, double* logp_dev, int
                 launch_map(st, ctx->d, ctx->map_threads, ctx->map_lds, theta_dev, w0, n, ctx->d_img, nullptr, nullptr, nullptr, false);
             }
             if (tm) HIPCHK(ctx, hipEventRecord(es.e[2], st));
-            {
+            if (contract) {
+                // the contracted partials added in pair order, chi^2, total, acceptance: 16 walkers x nflux values per block
+                JxDev dtl = d;
+                dtl.xr_split = xr_split ? 1 : 0;
+                dtl.xr_out = ctx->d_xr;
+                const unsigned tth = (unsigned)std::min(JX_RST_THREADS, 64 * ((16 * d.nflux + 63) / 64));
+                if (tm2 && es.p1stage == 4) HIPCHK(ctx, hipEventRecord(es.e[2], st));
+                hipLaunchKernelGGL((jx_rowsum_tail_kernel<0, true>), dim3((unsigned)((n + 15) / 16)), dim3(tth), sizeof(double) * 16 * (size_t)(d.nflux + 1), st,
+                                   dtl, ro, ctx->d_cfac, ctx->d_sz0, ctx->d_base, logp_dev, w0, (double*)nullptr, (double*)nullptr, t.chisq, t.parts, smv);
+                if (tm2 && es.p1stage == 4) HIPCHK(ctx, hipEventRecord(es.e[3], st));
+            } else {
                 JxDev dtl = d;
                 dtl.xr_split = xr_split ? 1 : 0;
                 dtl.xr_out = ctx->d_xr;
@@ -2738,6 +2783,10 @@ int jx_eval_stage(jx_ctx* ctx, const double* theta, int nwalkers, int stage, dou
     Taps t = all_taps(ctx, profiles);
     t.need_img = (stage == JX_STAGE_Y2D);
     t.need_conv = (stage == JX_STAGE_CONV2D);
+    // exact form with contracted partials: chi^2 and the parts come from the launches jx_eval runs (no row, no brightness: those two taps
+    // would bring the partial rows back); every other stage, and every other form, keeps all its taps
+    if ((stage == JX_STAGE_CHISQ || stage == JX_STAGE_PARTS) && !via_ref && ctx->conv_mode == 2 && ctx->mix.form == 2 && ctx->mix.x_pairwise &&
+        ctx->mix.x_contract && ctx->mix.x_ct_ok) { t.row = nullptr; t.bright = nullptr; }
     const int step = via_ref ? ctx->fft.cap : ctx->chunk;
     for (int w0 = 0; w0 < nwalkers; w0 += step) {
         const int n = std::min(step, nwalkers - w0);
@@ -2946,6 +2995,17 @@ int jx_get_conv_layout(jx_ctx* ctx, int32_t out[12]) {
     }
     out[0] = m.form; out[1] = ctx->qn; out[2] = m.r; out[3] = m.ns; out[4] = m.form == 0 ? m.mx.R : 0; out[5] = m.RT;
     out[6] = m.nxt; out[7] = m.og.ntile; out[8] = m.ksteps; out[9] = (int32_t)m.tW; out[10] = m.og.ldx; out[11] = m.last_ksplit;
+    return JX_OK;
+}
+
+int jx_get_exact_info(jx_ctx* ctx, int32_t out[8]) {
+    if (!ctx || !ctx->finalized || !out) return JX_ERR_STATE;
+    const MixBack& m = ctx->mix;
+    if (ctx->conv_mode != 2 || m.form != 2) { ctx->err = "the exact form is not in use"; return JX_ERR_UNSUPPORTED; }
+    const bool ct = m.x_pairwise && m.x_contract && m.x_ct_ok;
+    out[0] = ct ? 1 : 0; out[1] = m.x_ldm; out[2] = 16 * m.x_nxt * m.x_ng_use; out[3] = m.x_last_ct;
+    out[4] = m.x_lde ? 1 : 0; out[5] = (int32_t)std::min<size_t>(sizeof(double) * ((size_t)m.x_o_E + (size_t)ctx->d.nflux * m.x_lde), (size_t)INT32_MAX);
+    out[6] = out[7] = 0;
     return JX_OK;
 }
 

@@ -20,6 +20,11 @@
 //   jx_rowsum_tail_kernel   adds a walker tile's partial rows in pair order, then conversion factors, the not-a-knot spline to the
 //                           data radii (a constant nflux x nrow matrix), chi^2, total, and -- inside jx_sample -- the acceptance
 //                           of the stretch move.  One block per 16 walkers.
+//                           Contracted form (default for every call without a row or brightness tap; JOXSZ_X_CONTRACT=0 switches it off):
+//                           conversion factors and the data-radii matrix are linear too, with per-walker and constant coefficients, so
+//                           jx_ordrow_kernel applies them to ITS share of the row -- E (cfac . share), [16][nflux] values per pair instead
+//                           of [16][outputs]: 19 for 96 at 512^2 -- and this kernel adds the pairs' shares of the model at the data radii in
+//                           pair order, then chi^2, total, acceptance.
 //   jx_rowop_tail_kernel    the same two steps as ONE block per 16 walkers reading the ordinates back (K cut over eight waves):
 //                           fewer, longer blocks; kept as the reference form of the pair-wise kernel (JOXSZ_X_PAIRWISE=0).
 //
@@ -54,6 +59,16 @@ struct JxRowOp {
     const double* pp;              // [n][ldpp] pressure profiles (jx_prep_kernel)
     double* y;                     // [tW][ldy] ordinates, walker-major; null: not stored (timed path: nothing reads them)
     double* P;                     // [walker tiles][npair][ng_all][16][16 NXT] partial rows
+    // contracted form (JOXSZ_X_CONTRACT, calls without row / brightness taps): the pair's share of the row goes through the conversion
+    // factors and the data-radii matrix inside jx_ordrow_kernel, and what crosses to the tail is its share of the model at the data radii
+    int nflux, nrow;               // data radii; doubles per walker of cfac and per data radius of emat
+    int ldm;                       // doubles per walker of a contracted partial (>= nflux)
+    int o_z, o_E;                  // LDS offsets (doubles) of jx_ordrow_kernel's epilogue behind the [16][ldr] converted share at 0 (over the dead reduction area,
+                                   // and over the pair's ordinates where it is longer): [4][16][nflux + 1] wave sums, [nflux][lde] data-radii matrix
+    const double* cfac;            // [n][nrow] conversion factors (per-walker kernel)
+    const double* emat;            // [nflux][nrow] data-radii matrix
+    const double* Ec;              // [nflux][lde] the same, the outputs in use only, rows padded to the LDS stride
+    double* Pm;                    // [walker tiles][npair][16][ldm] contracted partials
     long long* stamps;             // diagnostic build only: [blocks][8] wall-clock stamps (100 MHz) of jx_ordrow_kernel's phases
 };
 #ifdef JOXSZ_ABLATIONS
@@ -70,17 +85,16 @@ struct JxRowOp {
 // multiply-adds; the waves' partial sums are added in wave order.
 // ------------------------------------------------------------------------------------------------------------------
 template <int ND, bool ELDS>
-__device__ __forceinline__ void jx_row_dots(const JxDev& c, const JxRowOp& g, const double* __restrict__ s_row, double* __restrict__ s_z,
-                                            const double* __restrict__ s_E, int i0) {
+__device__ __forceinline__ void jx_row_dots(int nflux, int nrow, const double* __restrict__ em, const JxRowOp& g, const double* __restrict__ s_row,
+                                            double* __restrict__ s_z, const double* __restrict__ s_E, int i0) {
     const int tid = threadIdx.x, nwv = blockDim.x >> 6, wv = tid >> 6, lane = tid & 63, w = lane & 15, dq = lane >> 4;
-    const int nflux = c.nflux, nuse = g.nuse, nrow = c.nrow;
+    const int nuse = g.nuse;
     const int xw = (nuse + nwv - 1) / nwv, x0 = min(wv * xw, nuse), x1 = min(nuse, x0 + xw);
     double acc[ND];
     int eo[ND];
 #pragma unroll
     for (int i = 0; i < ND; ++i) { acc[i] = 0.0; eo[i] = min(dq + 4 * (i0 + i), nflux - 1) * (ELDS ? g.lde : nrow); }   // (a data radius beyond the last repeats it: never stored)
     const double* __restrict__ br = s_row + (size_t)w * g.ldr;
-    const double* __restrict__ em = c.emat;
     for (int x = x0; x < x1; ++x) {
         const double b = br[x];
 #pragma unroll
@@ -93,51 +107,37 @@ __device__ __forceinline__ void jx_row_dots(const JxDev& c, const JxRowOp& g, co
     }
 }
 
-template <bool CONVERTED /* s_row already carries the conversion factors (and the brightness tap is written) */>
-__device__ __forceinline__ void jx_row_epilogue(const JxDev& c, const JxRowOp& g, int wb, double* s_row, double* s_z, const double* s_E,
-                                                const double* __restrict__ cfac, const double* __restrict__ sz0, const double* __restrict__ base,
-                                                double* __restrict__ logp, int w0, double* __restrict__ tap_bright, double* __restrict__ tap_chisq,
-                                                double* __restrict__ tap_parts, const JxSm& smv) {
-    const int tid = threadIdx.x, nth = blockDim.x, nrow = c.nrow, nflux = c.nflux, nuse = g.nuse, ldr = g.ldr;
-    // (what the last steps read from memory is requested here, ahead of the products)
-    const bool fin = tid < 16 && wb + tid < g.n;
-    const double pre_base = fin ? base[wb + tid] : 0.0, pre_sz0 = (fin && sz0) ? sz0[wb + tid] : 0.0;
-    const double pre_xl = (fin && c.xr_split) ? c.xr_out[2 * (size_t)(wb + tid)] : 0.0, pre_xb = (fin && c.xr_split) ? c.xr_out[2 * (size_t)(wb + tid) + 1] : 0.0;
-    double pre_f[2], pre_e[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) { const int d = min((tid + u * nth) >> 4, nflux - 1); pre_f[u] = c.flux[nflux + d]; pre_e[u] = c.flux[2 * nflux + d]; }
-    if (!CONVERTED) {
-        for (int idx = tid; idx < 16 * nuse; idx += nth) {
-            const int w = idx / nuse, x = idx - w * nuse;
-            const size_t o = (size_t)min(wb + w, g.n - 1) * nrow + x;
-            const double b = s_row[w * ldr + x] * cfac[o];
-            s_row[w * ldr + x] = b;
-            if (tap_bright && wb + w < g.n) tap_bright[o] = b;
-        }
-        __syncthreads();
-    }
+// the nflux x nuse products of a block's 16 walkers, every data radius (called by every thread; the caller puts a barrier behind it)
+__device__ __forceinline__ void jx_row_dots_all(int nflux, int nrow, const double* __restrict__ em, const JxRowOp& g, const double* s_row, double* s_z, const double* s_E) {
     const int ni = (nflux + 3) >> 2;                            // data radii per lane
-    if (ni <= 5) { if (g.lde) jx_row_dots<5, true>(c, g, s_row, s_z, s_E, 0); else jx_row_dots<5, false>(c, g, s_row, s_z, s_E, 0); }
-    else for (int i0 = 0; i0 < ni; i0 += 8) { if (g.lde) jx_row_dots<8, true>(c, g, s_row, s_z, s_E, i0); else jx_row_dots<8, false>(c, g, s_row, s_z, s_E, i0); }
-    __syncthreads();
-    const int nwv = nth >> 6;
-    for (int p = tid, u = 0; p < 16 * nflux; p += nth, ++u) {
-        const int w = p & 15, d = p >> 4;
-        double m = 0.0;
-        for (int v = 0; v < nwv; ++v) m += s_z[((size_t)v * 16 + w) * (nflux + 1) + d];
-        const double z = ((u < 2 ? pre_f[u & 1] : c.flux[nflux + d]) - m) / (u < 2 ? pre_e[u & 1] : c.flux[2 * nflux + d]);
-        const double z2 = z * z;
-        s_z[(size_t)w * (nflux + 1) + d] = (z2 == z2) ? z2 : 0.0;       // np.nansum drops NaN terms
-    }
-    __syncthreads();
+    if (ni <= 5) { if (g.lde) jx_row_dots<5, true>(nflux, nrow, em, g, s_row, s_z, s_E, 0); else jx_row_dots<5, false>(nflux, nrow, em, g, s_row, s_z, s_E, 0); }
+    else for (int i0 = 0; i0 < ni; i0 += 8) { if (g.lde) jx_row_dots<8, true>(nflux, nrow, em, g, s_row, s_z, s_E, i0); else jx_row_dots<8, false>(nflux, nrow, em, g, s_row, s_z, s_E, i0); }
+}
+
+// What the first 16 threads of a tail read from memory for their walker, requested ahead of the products
+struct JxFinPre { double base, sz0, xl, xb; };
+__device__ __forceinline__ JxFinPre jx_row_finish_loads(const JxDev& c, const JxRowOp& g, int wb, const double* __restrict__ sz0, const double* __restrict__ base) {
+    const int tid = threadIdx.x;
+    const bool fin = tid < 16 && wb + tid < g.n;
+    JxFinPre f;
+    f.base = fin ? base[wb + tid] : 0.0; f.sz0 = (fin && sz0) ? sz0[wb + tid] : 0.0;
+    f.xl = (fin && c.xr_split) ? c.xr_out[2 * (size_t)(wb + tid)] : 0.0; f.xb = (fin && c.xr_split) ? c.xr_out[2 * (size_t)(wb + tid) + 1] : 0.0;
+    return f;
+}
+
+// The last step of a tail: s_z[w][d] holds the chi^2 terms of the block's 16 walkers (behind a barrier); thread w < 16 adds them in order of
+// the data radius and forms the total (joxsz_funcs.py:478, 538) -- and, inside jx_sample, accepts or rejects the proposal.
+__device__ __forceinline__ void jx_row_finish(const JxDev& c, const JxRowOp& g, int wb, const double* s_z, const JxFinPre& pre,
+                                              double* __restrict__ logp, int w0, double* __restrict__ tap_chisq, double* __restrict__ tap_parts, const JxSm& smv) {
+    const int tid = threadIdx.x, nflux = c.nflux;
     if (tid < 16 && wb + tid < g.n) {
         const int w = wb + tid;
         double chisq = 0.0;
         for (int d = 0; d < nflux; ++d) chisq += s_z[(size_t)tid * (nflux + 1) + d];
-        const double ll = -chisq / 2.0 + pre_sz0;
-        double b = pre_base;
+        const double ll = -chisq / 2.0 + pre.sz0;
+        double b = pre.base;
         // (two-block form of the per-walker kernel: the priors arrive here, the Cash log-likelihood and its verdict beside them)
-        if (c.xr_split && b != -INFINITY) b = (pre_xb != 0.0) ? -INFINITY : b + pre_xl;
+        if (c.xr_split && b != -INFINITY) b = (pre.xb != 0.0) ? -INFINITY : b + pre.xl;
         double tot = (b == -INFINITY) ? -INFINITY : b + ll;
         if (tot != tot) tot = -INFINITY;                         // never hand NaN to the sampler
         logp[w0 + w] = tot;
@@ -159,15 +159,58 @@ __device__ __forceinline__ void jx_row_epilogue(const JxDev& c, const JxRowOp& g
     }
 }
 
+template <bool CONVERTED /* s_row already carries the conversion factors (and the brightness tap is written) */>
+__device__ __forceinline__ void jx_row_epilogue(const JxDev& c, const JxRowOp& g, int wb, double* s_row, double* s_z, const double* s_E,
+                                                const double* __restrict__ cfac, const double* __restrict__ sz0, const double* __restrict__ base,
+                                                double* __restrict__ logp, int w0, double* __restrict__ tap_bright, double* __restrict__ tap_chisq,
+                                                double* __restrict__ tap_parts, const JxSm& smv) {
+    const int tid = threadIdx.x, nth = blockDim.x, nrow = c.nrow, nflux = c.nflux, nuse = g.nuse, ldr = g.ldr;
+    // (what the last steps read from memory is requested here, ahead of the products)
+    const JxFinPre pre = jx_row_finish_loads(c, g, wb, sz0, base);
+    double pre_f[2], pre_e[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) { const int d = min((tid + u * nth) >> 4, nflux - 1); pre_f[u] = c.flux[nflux + d]; pre_e[u] = c.flux[2 * nflux + d]; }
+    if (!CONVERTED) {
+        for (int idx = tid; idx < 16 * nuse; idx += nth) {
+            const int w = idx / nuse, x = idx - w * nuse;
+            const size_t o = (size_t)min(wb + w, g.n - 1) * nrow + x;
+            const double b = s_row[w * ldr + x] * cfac[o];
+            s_row[w * ldr + x] = b;
+            if (tap_bright && wb + w < g.n) tap_bright[o] = b;
+        }
+        __syncthreads();
+    }
+    jx_row_dots_all(nflux, nrow, c.emat, g, s_row, s_z, s_E);
+    __syncthreads();
+    const int nwv = nth >> 6;
+    for (int p = tid, u = 0; p < 16 * nflux; p += nth, ++u) {
+        const int w = p & 15, d = p >> 4;
+        double m = 0.0;
+        for (int v = 0; v < nwv; ++v) m += s_z[((size_t)v * 16 + w) * (nflux + 1) + d];
+        const double z = ((u < 2 ? pre_f[u & 1] : c.flux[nflux + d]) - m) / (u < 2 ? pre_e[u & 1] : c.flux[2 * nflux + d]);
+        const double z2 = z * z;
+        s_z[(size_t)w * (nflux + 1) + d] = (z2 == z2) ? z2 : 0.0;       // np.nansum drops NaN terms
+    }
+    __syncthreads();
+    jx_row_finish(c, g, wb, s_z, pre, logp, w0, tap_chisq, tap_parts, smv);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Ordinate product + this pair's share of the row product.
 //   grid: 8 x ceil(walker tiles / 8) x npair blocks of 256 threads; block id & 7 picks the walker tiles of one XCD (the profiles
 //   of a tile and its partial rows then stay in one L2: speed only)
 //   LDS: [4 waves][2 tiles][16][16] partial ordinates, then [16][36] the pair's ordinates
+//
+// CT, the contracted form of the epilogue: everything between a pair's share of the row and the model at the data radii is linear with
+// constant or per-walker coefficients, m[w][d] = sum_x E[d][x] cfac[w][x] sum_pair P_pair[w][x], so the block applies the conversion
+// factors and the data-radii matrix to ITS share and stores [16][nflux] values in place of [16][outputs].  The products are jx_row_dots'
+// (a wave takes a quarter of the outputs in use, wave sums added in wave order): grouped by the problem alone, like every other sum.
+//   LDS: [16][ldr] converted share over the dead reduction area (and, behind one more barrier, over the pair's ordinates where it is
+//   longer), then [4][16][nflux + 1] wave sums and [nflux][lde] data-radii matrix (JxRowOp::o_z, o_E)
 // ------------------------------------------------------------------------------------------------------------------
 #define JX_ORD_LDS_DOUBLES (4 * 2 * 256 + 16 * 36)
 
-template <int NXT>
+template <int NXT, bool CT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 jx_ordrow_kernel(JxRowOp g) {
     extern __shared__ __attribute__((aligned(16))) double sm_or[];
@@ -205,6 +248,33 @@ jx_ordrow_kernel(JxRowOp g) {
             }
         }
     };
+
+    // contracted form: the conversion factors of the wave's output tiles (lane: walker lk + 4 r, output 16 t + li, as the product leaves them)
+    double cfv[NTT][4];
+    auto load_cf = [&](int gi) {
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) {
+            const int X = min(gi * 16 * NXT + 16 * min(wv + 4 * tt, NXT - 1) + li, g.nrow - 1);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) cfv[tt][r] = g.cfac[(size_t)min(wb + lk + 4 * r, g.n - 1) * g.nrow + X];
+        }
+    };
+    if (CT) {
+        // requested here, ahead of the k loop: the first group's factors stay in registers, the data-radii matrix goes to LDS (one trip,
+        // beside the first operands of the loop)
+        load_cf(0);
+        if (g.lde) {
+            double* s_Ec = sm_or + g.o_E;
+            const int tot = g.nflux * g.lde;
+            for (int i0 = 0; i0 < tot; i0 += 8 * 256) {
+                double ev[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) ev[u] = g.Ec[min(i0 + u * 256 + tid, tot - 1)];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int i = i0 + u * 256 + tid; if (i < tot) s_Ec[i] = ev[u]; }
+            }
+        }
+    }
 
     auto load_a = [&](int s) -> jx_ro_v4d { return *reinterpret_cast<const jx_ro_v4d*>(ppl + 16 * s); };   // (rows padded with zeros to 16 nSj)
     auto load_b = [&](int s, int t) -> jx_ro_v4d { return *reinterpret_cast<const jx_ro_v4d*>(tb + ((size_t)s * g.nS + t) * 256); };
@@ -263,8 +333,11 @@ jx_ordrow_kernel(JxRowOp g) {
     // ---- this pair's share of the row product: P[x] = sum over the pair's 32 ordinates of Wy[x][k] y[k]; wave v owns the output tiles v, v + 4
     const jx_ro_v4d yp = *reinterpret_cast<const jx_ro_v4d*>(s_yt + li * 36 + 4 * lk);
     const jx_ro_v4d yq = *reinterpret_cast<const jx_ro_v4d*>(s_yt + li * 36 + 16 + 4 * lk);
+    double* s_row = sm_or;                                      // (contracted form; the reduction area is dead behind the barrier above)
+    if (CT && 16 * g.ldr > 4 * 2 * 256) __syncthreads();         // (a share that reaches into the pair's ordinates: every wave has read them)
     for (int gi = 0; gi < (JX_DBG(g, 2) ? 0 : g.ng); ++gi) {
         load_op(gi);
+        if (CT && gi > 0) load_cf(gi);
         // folded form: pair p also takes the macro steps p, p + npair, ... of the last ordinate tile's share of the row, an operator on the
         // profile (requested with the row operator above: one trip; requesting both ahead of the reduction was measured twice: slower)
         const bool fold = p < g.nfold;
@@ -303,9 +376,33 @@ jx_ordrow_kernel(JxRowOp g) {
                     }
                 }
                 const jx_ro_v4d cs = c0 + c1;
+                if (CT) {
+                    const int X = gi * 16 * NXT + 16 * t + li;
+                    if (X < g.nuse) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) s_row[(lk + 4 * r) * g.ldr + X] = cs[r] * cfv[tt][r];
+                    }
+                } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (!JX_DBG(g, 4) || cs[r] == 1.234e300) Pb[(size_t)(lk + 4 * r) * (16 * NXT) + 16 * t + li] = cs[r];
+                }
             }
+        }
+    }
+    if (CT) {
+        // ---- the block's share of the model at the data radii: E (cfac . share), wave sums added in wave order
+        double* s_zc = sm_or + g.o_z;
+        const int nflux = g.nflux;
+        __syncthreads();
+        jx_row_dots_all(nflux, g.nrow, g.emat, g, s_row, s_zc, sm_or + g.o_E);
+        __syncthreads();
+        double* __restrict__ Pmb = g.Pm + ((size_t)wt * g.npair + p) * 16 * (size_t)g.ldm;
+        for (int i = tid; i < 16 * nflux; i += 256) {
+            const int w = i / nflux, d = i - w * nflux;
+            double m = 0.0;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) m += s_zc[((size_t)v * 16 + w) * (nflux + 1) + d];
+            if (wb + w < g.n && !JX_DBG(g, 4)) Pmb[(size_t)w * g.ldm + d] = m;
         }
     }
     JX_STAMP(g, 4);
@@ -318,12 +415,42 @@ jx_ordrow_kernel(JxRowOp g) {
 #define JX_RST_LDS_DOUBLES(ldr, nflux, lde) ((size_t)16 * (ldr) + (size_t)8 * 16 * ((nflux) + 1) + (size_t)(nflux) * (lde))
 
 #define JX_RST_THREADS 512
-template <int NXT>
+// CT, the tail of the contracted form (launched as <0, true>, any block size up to JX_RST_THREADS): the pairs' contracted partials
+// Pm[pair][16][ldm] added in pair order are the model at the data radii; what is left is chi^2, the total and the acceptance.
+//   LDS: [16][nflux + 1] chi^2 terms
+#define JX_RSTC_PAIRS 12               // pairs whose partials a thread requests together
+template <int NXT, bool CT = false>
 __global__ void __launch_bounds__(JX_RST_THREADS)
 jx_rowsum_tail_kernel(JxDev c, JxRowOp g, const double* __restrict__ cfac, const double* __restrict__ sz0, const double* __restrict__ base,
                       double* __restrict__ logp, int w0, double* __restrict__ tap_row, double* __restrict__ tap_bright,
                       double* __restrict__ tap_chisq, double* __restrict__ tap_parts, JxSm smv) {
     extern __shared__ __attribute__((aligned(16))) double sm_rs[];
+    if constexpr (CT) {
+        const int tid = threadIdx.x, nth = blockDim.x, wt = blockIdx.x, wb = wt * 16, nflux = c.nflux, tot = 16 * nflux;
+        // (every load of the block is requested before the first use: one trip to memory)
+        const JxFinPre pre = jx_row_finish_loads(c, g, wb, sz0, base);
+        const double* __restrict__ Pt = g.Pm + (size_t)wt * g.npair * 16 * (size_t)g.ldm;
+        const size_t ps = (size_t)16 * g.ldm;
+        for (int i0 = 0; i0 < tot; i0 += nth) {
+            const int i = i0 + tid, ic = min(i, tot - 1), w = ic / nflux, d = ic - w * nflux;
+            const double f = c.flux[nflux + d], e = c.flux[2 * nflux + d];
+            const double* __restrict__ Pw = Pt + (size_t)w * g.ldm + d;
+            double m = 0.0;
+            for (int pr0 = 0; pr0 < g.npair; pr0 += JX_RSTC_PAIRS) {      // (added in pair order)
+                double v[JX_RSTC_PAIRS];
+#pragma unroll
+                for (int u = 0; u < JX_RSTC_PAIRS; ++u) v[u] = Pw[(size_t)min(pr0 + u, g.npair - 1) * ps];
+#pragma unroll
+                for (int u = 0; u < JX_RSTC_PAIRS; ++u) if (pr0 + u < g.npair) m += v[u];
+            }
+            const double z = (f - m) / e;
+            const double z2 = z * z;
+            if (i < tot) sm_rs[(size_t)w * (nflux + 1) + d] = (z2 == z2) ? z2 : 0.0;       // np.nansum drops NaN terms
+        }
+        __syncthreads();
+        jx_row_finish(c, g, wb, sm_rs, pre, logp, w0, tap_chisq, tap_parts, smv);
+        return;
+    } else {
     constexpr int NX = 16 * NXT, MAXC = 3;
     const int tid = threadIdx.x, nth = blockDim.x;
     const int wt = blockIdx.x, wb = wt * 16, nrow = c.nrow, nuse = g.nuse, ldr = g.ldr;
@@ -371,6 +498,7 @@ jx_rowsum_tail_kernel(JxDev c, JxRowOp g, const double* __restrict__ cfac, const
     }
     __syncthreads();
     jx_row_epilogue<true>(c, g, wb, s_row, s_z, s_E, cfac, sz0, base, logp, w0, tap_bright, tap_chisq, tap_parts, smv);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ EXPORTS = (
     'jx_create', 'jx_upload', 'jx_finalize', 'jx_eval', 'jx_eval_device', 'jx_sync', 'jx_set_stream', 'jx_sample', 'jx_eval_stage',
     'jx_set_route', 'jx_get_route', 'jx_get_operator', 'jx_set_option', 'jx_audit',
     'jx_set_par_vals', 'jx_dev_alloc', 'jx_dev_free', 'jx_memcpy_h2d', 'jx_memcpy_d2h',
-    'jx_timing_reset', 'jx_timing_enable', 'jx_timing_get', 'jx_get_info', 'jx_get_conv_mode', 'jx_get_conv_layout', 'jx_get_fft_info', 'jx_debug_workspace', 'jx_device_count',
+    'jx_timing_reset', 'jx_timing_enable', 'jx_timing_get', 'jx_get_info', 'jx_get_conv_mode', 'jx_get_conv_layout', 'jx_get_exact_info', 'jx_get_fft_info', 'jx_debug_workspace', 'jx_device_count',
     'jx_device_name', 'jx_strerror', 'jx_last_error', 'jx_destroy',
     'jx_get_truncation', 'jx_get_output_pruning', 'jx_get_sampling', 'jx_get_radial_sampling', 'jx_comm_unique_id', 'jx_comm_init_rank', 'jx_allgather_logp', 'jx_comm_allreduce_max', 'jx_comm_destroy',
     'jx_comm_count', 'jx_comm_set_overlap', 'jx_comm_gather_time', 'jx_map_kernel_time', 'jx_event_bracket_time', 'jx_fastmath_eval', 'jx_copy_bandwidth', 'jx_stream_bandwidth',
@@ -96,6 +96,7 @@ def load_library(path=None):
     lib.jx_get_info.argtypes = [vp, i32p, i32p, i32p, i32p, i64p]
     lib.jx_get_conv_mode.argtypes = [vp]
     lib.jx_get_conv_layout.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+    lib.jx_get_exact_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     lib.jx_get_truncation.argtypes = [vp, dp]
     lib.jx_get_output_pruning.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     lib.jx_get_sampling.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ci]
@@ -256,6 +257,14 @@ class HipContext:
         d = dict(zip(('form', 'NU', 'rank', 'beam_terms', 'R', 'RT', 'nxt', 'ntile', 'ksteps', 'tW', 'ldx', 'ksplit'), [int(v) for v in lay]))
         d['form'] = ('lowrank', 'full', 'exact')[d['form']]
         return d
+
+    def exact_info(self):
+        """Exact form: what the row product hands to the tail (jx_get_exact_info) -- the contracted partials or partial rows, and which of the
+        two the last launch of this context used."""
+        o = (ctypes.c_int32 * 8)()
+        self._chk(self.lib.jx_get_exact_info(self._h, o), 'jx_get_exact_info')
+        return dict(contracted=bool(o[0]), doubles_per_contracted_partial=int(o[1]), doubles_per_partial_row=int(o[2]),
+                    last_launch={1: 'contracted', 0: 'partial rows'}.get(int(o[3])), data_radii_matrix_in_lds=bool(o[4]), lds_bytes=int(o[5]))
 
     def _truncation(self):
         tr = (ctypes.c_double * 12)()
