@@ -173,8 +173,9 @@ int  jx_finalize(jx_ctx* ctx);
  *                                                          (legacy: the cheaper of low-rank and full, as round 4 picked; they carry their own options below)
  *   JOXSZ_X_PAIRWISE             1|0 (1)                   exact form: 0 = its reference kernels (one block per 16 walkers reads the ordinates back; jx_rowop_tail_kernel)
  *   JOXSZ_X_CONTRACT             1|0 (1)                   exact form, calls without row / brightness taps: each block of the row product applies the conversion factors and the data-radii
- *                                                          matrix to its own share of the row and hands nflux values per walker to the tail instead of the share itself (19 for 96
- *                                                          at 512^2); 0: partial rows in every call, as calls with those taps exchange them (see jx_get_exact_info)
+ *                                                          matrix to its own share of the row -- a second matrix-core product straight from the accumulator registers of the first --
+ *                                                          and hands nflux values per walker to the tail instead of the share itself (19 for 96 at 512^2; up to 32 data radii);
+ *                                                          0: partial rows in every call, as calls with those taps exchange them (see jx_get_exact_info)
  *   JOXSZ_X_FOLD                 1|0 (1)                   exact form, timed path: the ordinates stay in LDS (nothing reads them), and with an odd number of 16-ordinate tiles the last tile's
  *                                                          share of the row is an operator on the profile inside the row product, the others in exact pairs (one block fewer per 16
  *                                                          walkers: 768 instead of 832 at 512^2 / 1024 walkers); 0: every tile through the ordinate product, ordinates stored (as calls with taps do)
@@ -344,11 +345,11 @@ int  jx_get_fft_info(jx_ctx* ctx, int32_t out[34]);
  * JX_ERR_UNSUPPORTED with the rocFFT back end. */
 int  jx_get_conv_layout(jx_ctx* ctx, int32_t out[12]);
 /* The exact form's exchange between the row product and the tail: out = {1 when calls without row / brightness taps take the contracted form
- * (JOXSZ_X_CONTRACT on, the pair-wise kernels, out[5] <= 52 KB -- three blocks in the 160 KB of a compute unit -- and out[1] < out[2]: where the
- * partial would not be smaller than the row, as on maps of 32 pixels, nothing is gained), doubles per walker of a contracted partial, doubles
- * per walker and pair of a partial row, form of the LAST launch of this context (1 contracted, 0 partial rows, -1 none yet), 1 when the
- * data-radii matrix of the contracted epilogue sits in LDS (0: it would not fit, read through the caches), bytes of LDS per block of the
- * contracted row product, 0, 0}.  JX_ERR_UNSUPPORTED unless the exact form is in use. */
+ * (JOXSZ_X_CONTRACT on, the pair-wise kernels, at most 32 data radii -- the two tiles of 16 the epilogue's matrix-core product is instantiated
+ * for -- and out[1] < out[2]: where the partial would not be smaller than the row, as on maps of 32 pixels, nothing is gained), doubles per
+ * walker of a contracted partial, doubles per walker and pair of a partial row, form of the LAST launch of this context (1 contracted, 0
+ * partial rows, -1 none yet), 0 (the data-radii matrix of the contracted epilogue is never in LDS: it is read in operand order through the
+ * caches), bytes of LDS per block of the row product of calls without those taps, 0, 0}.  JX_ERR_UNSUPPORTED unless the exact form is in use. */
 int  jx_get_exact_info(jx_ctx* ctx, int32_t out[8]);
 /* Which map samples stage 1 of the low-rank form evaluates: out = {distinct rows (= columns) of the map quadrant NU; rows stage 1
  * evaluates; full resolution below this many pixels from the axis; every second row up to here (u1), every fourth up to 2 u1, every eighth beyond; interpolation

@@ -86,9 +86,9 @@ struct MixBack {
     double *x_Typ = nullptr, *x_Opk = nullptr, *x_y = nullptr, *x_cf = nullptr, *x_P = nullptr, *x_ppi = nullptr;
     bool x_pairwise = true;            // JOXSZ_X_PAIRWISE=0: the ordinates read back by one block per 16 walkers (jx_rowop_tail_kernel)
     bool x_contract = true;            // JOXSZ_X_CONTRACT=0: the pair-wise kernels exchange partial rows in every call (with it: only in calls with row / brightness taps)
-    bool x_ct_ok = false;              // the contracted epilogue fits this problem (LDS at three blocks per compute unit, fewer data radii than outputs)
-    int x_ldm = 0, x_ldr = 0, x_lde = 0, x_o_z = 0, x_o_E = 0, x_last_ct = -1;   // its geometry (JxRowOp); form of the last launch (-1: none yet)
-    double *x_Pm = nullptr, *x_Ec = nullptr;   // contracted partials [tW / 16][x_npair][16][x_ldm]; data-radii matrix [nflux][x_lde], the outputs in use
+    bool x_ct_ok = false;              // the contracted epilogue fits this problem (at most JX_CT_NDT tiles of data radii, fewer data radii than outputs)
+    int x_ldm = 0, x_ndt = 0, x_last_ct = -1;   // its geometry (JxRowOp); form of the last launch (-1: none yet)
+    double *x_Pm = nullptr, *x_Eop = nullptr;   // contracted partials [tW / 16][x_npair][16][x_ldm]; data-radii matrix as an operand [x_ng_use][x_nxt][x_ndt][64][4]
     JxMix mx{};
     JxOpg og{};
     JxOpg og_u{};                      // the product restricted to the outputs the tail reads (nxt_u tiles per block, ksplit_u slices); og: every output (taps)
@@ -986,21 +986,18 @@ static int mix_setup(jx_ctx* ctx, const MixBuild& mb, long long tW) {
         if ((rc = dev_new_l(ctx, m.allocs, (size_t)tW * m.Nkp, &m.x_y, true))) return rc;
         if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.x_npair * m.x_ng * 256 * m.x_nxt, &m.x_P, true))) return rc;
         {
-            // contracted form of the pair-wise kernels: the epilogue's LDS behind the ordinate product's, three blocks per compute unit resident
+            // contracted form of the pair-wise kernels: as many data-radii tiles as the epilogue is instantiated for, and fewer data radii than
+            // outputs (or the partial rows are the smaller ones); the data-radii matrix in the order its product reads it
             const int nflux = ctx->d.nflux, nrow = ctx->nrow, nuse = std::min(ctx->prune ? ctx->nrow_use : nrow, nrow);
-            m.x_ldr = (nuse + 1) | 1; m.x_lde = m.x_ldr; m.x_ldm = nflux;
-            m.x_o_z = std::max(JX_ORD_LDS_DOUBLES, 16 * m.x_ldr);
-            m.x_o_E = m.x_o_z + 4 * 16 * (nflux + 1);
-            const size_t lds_ct = (size_t)52 * 1024;
-            if (sizeof(double) * ((size_t)m.x_o_E + (size_t)nflux * m.x_lde) > lds_ct) m.x_lde = 0;     // (the data-radii matrix through the caches then)
-            m.x_ct_ok = sizeof(double) * ((size_t)m.x_o_E + (size_t)nflux * m.x_lde) <= lds_ct && nflux < 16 * m.x_nxt * m.x_ng_use;
-            m.x_Pm = nullptr; m.x_Ec = nullptr; m.x_last_ct = -1;
+            m.x_ldm = nflux; m.x_ndt = (nflux + 15) / 16;
+            m.x_ct_ok = m.x_ndt <= JX_CT_NDT && nflux < 16 * m.x_nxt * m.x_ng_use;
+            m.x_Pm = nullptr; m.x_Eop = nullptr; m.x_last_ct = -1;
             if (m.x_ct_ok) {
                 if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.x_npair * 16 * m.x_ldm, &m.x_Pm, true))) return rc;
-                if (m.x_lde) {
-                    if ((rc = dev_new_l(ctx, m.allocs, (size_t)nflux * m.x_lde, &m.x_Ec, true))) return rc;
-                    HIPCHK(ctx, hipMemcpy2D(m.x_Ec, sizeof(double) * m.x_lde, ctx->d.emat, sizeof(double) * nrow, sizeof(double) * nuse, nflux, hipMemcpyDeviceToDevice));
-                }
+                std::vector<double> hE((size_t)nflux * nrow), eop;
+                HIPCHK(ctx, hipMemcpy(hE.data(), ctx->d.emat, sizeof(double) * hE.size(), hipMemcpyDeviceToHost));
+                jxt::contract_operand_layout(hE.data(), nflux, nrow, nuse, m.x_nxt, m.x_ng_use, eop);
+                if ((rc = dev_put_l(ctx, m.allocs, eop.data(), eop.size(), &m.x_Eop))) return rc;
             }
         }
         m.bytes = ctx->device_bytes - before;
@@ -1988,7 +1985,10 @@ static int run_chunk(jx_ctx* ctx, const double* theta_dev, double* logp_dev, int
         const unsigned pgrid = xr_split ? 2u * (unsigned)n : (unsigned)n, pthr = xr_split ? 128u : (unsigned)JX_PREP_THREADS;
         if (xr_split && ctx->prep_lean && ctx->prep_fastmath && pp_buf && sizeof(double) * JX_W2_LDS_DOUBLES(d) <= (size_t)19 * 1024 + 512) {
             // the two-block form as two lean roles (same arithmetic, same bits; every table of a role in one batched copy into LDS)
-            hipLaunchKernelGGL(jx_walker2_kernel, dim3(pgrid), dim3(JX_W2_THREADS), sizeof(double) * JX_W2_LDS_DOUBLES(d), ps, dp, theta_dev, w0, base_buf, cfac_buf, pp_buf, smv);
+            // conversion factors up to the outputs this launch's consumers read: the exact form without taps reads those of the groups in use
+            // (jx_ordrow_kernel, the tails), every other consumer all of them
+            const int ncf = exact ? std::min(d.nrow, 16 * ctx->mix.x_nxt * ctx->mix.x_ng_use) : d.nrow;
+            hipLaunchKernelGGL(jx_walker2_kernel, dim3(pgrid), dim3(JX_W2_THREADS), sizeof(double) * JX_W2_LDS_DOUBLES(d), ps, dp, theta_dev, w0, base_buf, cfac_buf, pp_buf, ncf, smv);
             return;
         }
         const size_t sh = sizeof(double) * (JX_LDS_HDR + (size_t)2 * d.N + 2 * d.nann + 2 * (size_t)d.nband * d.nann + 2 * (size_t)d.nconv + 8 + JX_FM_TABLE_DOUBLES);
@@ -2131,9 +2131,8 @@ static int run_chunk(jx_ctx* ctx, const double* theta_dev, double* logp_dev, int
             // walker's bits must not depend on them); where it does not fit, or is switched off, the partial rows as before
             const bool contract = pairwise && m.x_contract && m.x_ct_ok && !all;
             if (contract) {
-                ro.nflux = d.nflux; ro.nrow = d.nrow; ro.ldm = m.x_ldm; ro.ldr = m.x_ldr; ro.lde = m.x_lde;
-                ro.o_z = m.x_o_z; ro.o_E = m.x_o_E;
-                ro.cfac = ctx->d_cfac; ro.emat = d.emat; ro.Ec = m.x_Ec; ro.Pm = m.x_Pm;
+                ro.nflux = d.nflux; ro.nrow = d.nrow; ro.ldm = m.x_ldm; ro.ndt = m.x_ndt;
+                ro.cfac = ctx->d_cfac; ro.Eop = m.x_Eop; ro.Pm = m.x_Pm;
             }
             m.x_last_ct = contract ? 1 : 0;
             {
@@ -2141,7 +2140,7 @@ static int run_chunk(jx_ctx* ctx, const double* theta_dev, double* logp_dev, int
                 if (!pairwise) r1.ng = 0;                        // (the ordinates alone: the row product reads them back)
                 const int ntw = (n + 15) / 16;
                 const dim3 grid((unsigned)(8 * ((ntw + 7) / 8) * r1.npair));
-                const size_t sh1 = sizeof(double) * (contract ? (size_t)ro.o_E + (size_t)ro.nflux * ro.lde : (size_t)JX_ORD_LDS_DOUBLES);
+                const size_t sh1 = sizeof(double) * (contract ? (size_t)JX_ORD_CT_LDS_DOUBLES(ro.ndt) : (size_t)JX_ORD_LDS_DOUBLES);
                 if (tm2 && es.p1stage == 2) HIPCHK(ctx, hipEventRecord(es.e[2], st));
                 bool done = false;
 #define JX_ORD_GO(Xv) if (!done && m.x_nxt == Xv) { \
@@ -3004,7 +3003,7 @@ int jx_get_exact_info(jx_ctx* ctx, int32_t out[8]) {
     if (ctx->conv_mode != 2 || m.form != 2) { ctx->err = "the exact form is not in use"; return JX_ERR_UNSUPPORTED; }
     const bool ct = m.x_pairwise && m.x_contract && m.x_ct_ok;
     out[0] = ct ? 1 : 0; out[1] = m.x_ldm; out[2] = 16 * m.x_nxt * m.x_ng_use; out[3] = m.x_last_ct;
-    out[4] = m.x_lde ? 1 : 0; out[5] = (int32_t)std::min<size_t>(sizeof(double) * ((size_t)m.x_o_E + (size_t)ctx->d.nflux * m.x_lde), (size_t)INT32_MAX);
+    out[4] = 0; out[5] = (int32_t)(sizeof(double) * (ct ? (size_t)JX_ORD_CT_LDS_DOUBLES(m.x_ndt) : (size_t)JX_ORD_LDS_DOUBLES));
     out[6] = out[7] = 0;
     return JX_OK;
 }

@@ -48,8 +48,8 @@ struct JxRowOp {
     int ldy;                       // doubles per walker of the ordinate array (= Nkp)
     int ng;                        // output groups of this launch: those the data-radii spline reads, or all of them (row / brightness taps)
     int nuse;                      // outputs the data-radii matrix reads (<= 16 NXT ng)
-    int ldr;                       // doubles per walker of the row in LDS (odd, > nuse)
-    int lde;                       // doubles per data radius of the data-radii matrix in LDS; 0: read from memory
+    int ldr;                       // tails: doubles per walker of the row in LDS (odd, > nuse)
+    int lde;                       // tails: doubles per data radius of the data-radii matrix in LDS; 0: read from memory
     int dbg;                       // diagnostic build only (make ABLATIONS=1; JOXSZ_X_DBG): 1 no matrix instructions in the ordinate product, 2 no row product, 4 no partial-row stores, 8 no operator loads
     int ldpp, nSj, npair;          // ordinate product: doubles per profile (16 nSj, zeros behind the grid), macro steps of 16 radii, column-tile pairs
     int nfold, s0f;                // folded form (odd nS, timed path): macro steps of 16 radii of the last ordinate tile's share of the row, the first of them; 0: none
@@ -61,13 +61,11 @@ struct JxRowOp {
     double* P;                     // [walker tiles][npair][ng_all][16][16 NXT] partial rows
     // contracted form (JOXSZ_X_CONTRACT, calls without row / brightness taps): the pair's share of the row goes through the conversion
     // factors and the data-radii matrix inside jx_ordrow_kernel, and what crosses to the tail is its share of the model at the data radii
-    int nflux, nrow;               // data radii; doubles per walker of cfac and per data radius of emat
+    int nflux, nrow;               // data radii; doubles per walker of cfac
+    int ndt;                       // data-radii tiles of 16 (<= JX_CT_NDT)
     int ldm;                       // doubles per walker of a contracted partial (>= nflux)
-    int o_z, o_E;                  // LDS offsets (doubles) of jx_ordrow_kernel's epilogue behind the [16][ldr] converted share at 0 (over the dead reduction area,
-                                   // and over the pair's ordinates where it is longer): [4][16][nflux + 1] wave sums, [nflux][lde] data-radii matrix
-    const double* cfac;            // [n][nrow] conversion factors (per-walker kernel)
-    const double* emat;            // [nflux][nrow] data-radii matrix
-    const double* Ec;              // [nflux][lde] the same, the outputs in use only, rows padded to the LDS stride
+    const double* cfac;            // [n][nrow] conversion factors (per-walker kernel), written up to the outputs of this launch's groups
+    const double* Eop;             // [ng][NXT][ndt][64][4] data-radii matrix as the A operand of the epilogue's product (jxt::contract_operand_layout)
     double* Pm;                    // [walker tiles][npair][16][ldm] contracted partials
     long long* stamps;             // diagnostic build only: [blocks][8] wall-clock stamps (100 MHz) of jx_ordrow_kernel's phases
 };
@@ -203,12 +201,19 @@ __device__ __forceinline__ void jx_row_epilogue(const JxDev& c, const JxRowOp& g
 //
 // CT, the contracted form of the epilogue: everything between a pair's share of the row and the model at the data radii is linear with
 // constant or per-walker coefficients, m[w][d] = sum_x E[d][x] cfac[w][x] sum_pair P_pair[w][x], so the block applies the conversion
-// factors and the data-radii matrix to ITS share and stores [16][nflux] values in place of [16][outputs].  The products are jx_row_dots'
-// (a wave takes a quarter of the outputs in use, wave sums added in wave order): grouped by the problem alone, like every other sum.
-//   LDS: [16][ldr] converted share over the dead reduction area (and, behind one more barrier, over the pair's ordinates where it is
-//   longer), then [4][16][nflux + 1] wave sums and [nflux][lde] data-radii matrix (JxRowOp::o_z, o_E)
+// factors and the data-radii matrix to ITS share and stores [16][nflux] values in place of [16][outputs].  Both products stay on the
+// matrix cores and the share never leaves the registers: the row product is formed TRANSPOSED, mfma(Op, y) in place of mfma(y, Op) -- the
+// same two registers read as A[x = li][k] and B[k][w = li], every element the same products in the same order, D[x = lk + 4 r][w = li]
+// -- so that register r of a lane, times its conversion factor cfac[w = li][X = 16 tile + lk + 4 r], IS the B operand B[k = lk][w = li]
+// of sub-step r of the next product, whose A operand A[d = li][k = lk] = E[16 dt + li][X] comes in operand order through the caches
+// (JxRowOp::Eop).  A wave accumulates m^T[d = lk + 4 r][w = li] over the sub-steps of a tile, its tiles in ascending order and the
+// groups in ascending order; the waves' sums are added in wave order: grouped by the problem alone, like every other sum.  A walker
+// lives in ONE column of every operand and result: a NaN or rejected walker touches nothing but its own values.
+//   LDS: [4][ndt][16][16] wave sums over the dead reduction area (JX_ORD_CT_LDS_DOUBLES); one barrier
 // ------------------------------------------------------------------------------------------------------------------
 #define JX_ORD_LDS_DOUBLES (4 * 2 * 256 + 16 * 36)
+#define JX_CT_NDT 2                    // data-radii tiles of 16 the contracted epilogue is instantiated for (nflux <= 32; beyond: partial rows)
+#define JX_ORD_CT_LDS_DOUBLES(ndt) ((4 * (ndt) * 256 + 16 * 36) > JX_ORD_LDS_DOUBLES ? (4 * (ndt) * 256 + 16 * 36) : JX_ORD_LDS_DOUBLES)
 
 template <int NXT, bool CT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
@@ -236,11 +241,12 @@ jx_ordrow_kernel(JxRowOp g) {
     for (int e = 0; e < 2; ++e) { ap[e] = jx_ro_v4d{0.0, 0.0, 0.0, 0.0}; aq[e] = jx_ro_v4d{0.0, 0.0, 0.0, 0.0}; }
     constexpr int NTT = (NXT + 3) / 4;
     double bpv[NTT][4], bqv[NTT][4];
+    int lane_g = lane;                                          // (the lane again, for the addresses of the row product's groups: see there)
     auto load_op = [&](int gi) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
             const int t = min(wv + 4 * tt, NXT - 1);
-            const double* __restrict__ ob = g.Opk + ((size_t)gi * g.nS * 256 + lane) * NXT + t;
+            const double* __restrict__ ob = g.Opk + ((size_t)gi * g.nS * 256 + lane_g) * NXT + t;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 bpv[tt][e] = ob[((size_t)p * 4 + e) * 64 * NXT];
@@ -249,32 +255,30 @@ jx_ordrow_kernel(JxRowOp g) {
         }
     };
 
-    // contracted form: the conversion factors of the wave's output tiles (lane: walker lk + 4 r, output 16 t + li, as the product leaves them)
+    // contracted form: the conversion factors of the wave's output tiles as the TRANSPOSED product leaves them (lane: walker li, outputs
+    // 16 t + lk + 4 r).  The k loop and the row product leave no 16 registers for them at four waves per SIMD (requested ahead of the k loop
+    // the build spills them), so they are requested with the data-radii matrix, behind the row product.  (One value per lane of their
+    // lines requested ahead of the k loop, to have them in this XCD's L2 by then: measured, 0.15 us slower per step, not kept.)
     double cfv[NTT][4];
     auto load_cf = [&](int gi) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
-            const int X = min(gi * 16 * NXT + 16 * min(wv + 4 * tt, NXT - 1) + li, g.nrow - 1);
+            const int X0 = gi * 16 * NXT + 16 * min(wv + 4 * tt, NXT - 1) + lk;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) cfv[tt][r] = g.cfac[(size_t)min(wb + lk + 4 * r, g.n - 1) * g.nrow + X];
+            for (int r = 0; r < 4; ++r) cfv[tt][r] = g.cfac[(size_t)wq * g.nrow + min(X0 + 4 * r, g.nrow - 1)];
         }
     };
-    if (CT) {
-        // requested here, ahead of the k loop: the first group's factors stay in registers, the data-radii matrix goes to LDS (one trip,
-        // beside the first operands of the loop)
-        load_cf(0);
-        if (g.lde) {
-            double* s_Ec = sm_or + g.o_E;
-            const int tot = g.nflux * g.lde;
-            for (int i0 = 0; i0 < tot; i0 += 8 * 256) {
-                double ev[8];
+    // ... and the data-radii matrix in operand order (jxt::contract_operand_layout): one 32-byte load per lane, output tile and data-radii tile
+    jx_ro_v4d ev[NTT][JX_CT_NDT];
+    auto load_e = [&](int gi) {
 #pragma unroll
-                for (int u = 0; u < 8; ++u) ev[u] = g.Ec[min(i0 + u * 256 + tid, tot - 1)];
+        for (int tt = 0; tt < NTT; ++tt) {
+            const int t = min(wv + 4 * tt, NXT - 1);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { const int i = i0 + u * 256 + tid; if (i < tot) s_Ec[i] = ev[u]; }
-            }
+            for (int dt = 0; dt < JX_CT_NDT; ++dt)
+                ev[tt][dt] = *reinterpret_cast<const jx_ro_v4d*>(g.Eop + ((((size_t)gi * NXT + t) * g.ndt + min(dt, g.ndt - 1)) * 64 + lane_g) * 4);
         }
-    }
+    };
 
     auto load_a = [&](int s) -> jx_ro_v4d { return *reinterpret_cast<const jx_ro_v4d*>(ppl + 16 * s); };   // (rows padded with zeros to 16 nSj)
     auto load_b = [&](int s, int t) -> jx_ro_v4d { return *reinterpret_cast<const jx_ro_v4d*>(tb + ((size_t)s * g.nS + t) * 256); };
@@ -333,11 +337,17 @@ jx_ordrow_kernel(JxRowOp g) {
     // ---- this pair's share of the row product: P[x] = sum over the pair's 32 ordinates of Wy[x][k] y[k]; wave v owns the output tiles v, v + 4
     const jx_ro_v4d yp = *reinterpret_cast<const jx_ro_v4d*>(s_yt + li * 36 + 4 * lk);
     const jx_ro_v4d yq = *reinterpret_cast<const jx_ro_v4d*>(s_yt + li * 36 + 16 + 4 * lk);
-    double* s_row = sm_or;                                      // (contracted form; the reduction area is dead behind the barrier above)
-    if (CT && 16 * g.ldr > 4 * 2 * 256) __syncthreads();         // (a share that reaches into the pair's ordinates: every wave has read them)
+    double* s_m = sm_or;                                        // contracted form: [4][ndt][16][16] wave sums (the reduction area is dead behind the barrier above)
     for (int gi = 0; gi < (JX_DBG(g, 2) ? 0 : g.ng); ++gi) {
+#ifdef __HIP_DEVICE_COMPILE__
+        // (contracted form: the lane number is made opaque per group, so that the lane parts of the operand addresses are formed where they
+        //  are used and die there, instead of being kept in registers from in front of the loop: the epilogue's operands need them.  This
+        //  steers the register allocator and nothing else: after a compiler change re-check with
+        //  make EXTRA=-Rpass-analysis=kernel-resource-usage that <6, true> has 0 bytes of scratch at four waves per SIMD)
+        if (CT) asm volatile("" : "+v"(lane_g));
+#endif
         load_op(gi);
-        if (CT && gi > 0) load_cf(gi);
+        double bv[NTT][4];
         // folded form: pair p also takes the macro steps p, p + npair, ... of the last ordinate tile's share of the row, an operator on the
         // profile (requested with the row operator above: one trip; requesting both ahead of the reduction was measured twice: slower)
         const bool fold = p < g.nfold;
@@ -348,7 +358,7 @@ jx_ordrow_kernel(JxRowOp g) {
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
                 const int t = min(wv + 4 * tt, NXT - 1);
-                const double* __restrict__ ob = g.Wfk + ((((size_t)gi * g.nfold + p) * 4) * 64 + lane) * NXT + t;
+                const double* __restrict__ ob = g.Wfk + ((((size_t)gi * g.nfold + p) * 4) * 64 + lane_g) * NXT + t;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) bfv[tt][e] = ob[(size_t)e * 64 * NXT];
             }
@@ -360,48 +370,74 @@ jx_ordrow_kernel(JxRowOp g) {
             if (t < NXT) {                                       // (wave-uniform)
                 jx_ro_v4d c0 = jx_ro_v4d{0.0, 0.0, 0.0, 0.0}, c1 = jx_ro_v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(yp[e], bpv[tt][e], c0, 0, 0, 0);
+                for (int e = 0; e < 4; ++e) c0 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(bpv[tt][e], yp[e], c0, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(yp[e], bpv[tt][e], c0, 0, 0, 0);
                 if (hasq) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(yq[e], bqv[tt][e], c1, 0, 0, 0);
+                    for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(bqv[tt][e], yq[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(yq[e], bqv[tt][e], c1, 0, 0, 0);
                 }
                 if (fold) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(af[e], bfv[tt][e], c1, 0, 0, 0);
+                    for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(bfv[tt][e], af[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(af[e], bfv[tt][e], c1, 0, 0, 0);
                     for (int sf = p + g.npair; sf < g.nfold; sf += g.npair) {        // (more macro steps than pairs: short grids only)
                         const jx_ro_v4d a2 = load_a(g.s0f + sf);
-                        const double* __restrict__ ob = g.Wfk + ((((size_t)gi * g.nfold + sf) * 4) * 64 + lane) * NXT + t;
+                        const double* __restrict__ ob = g.Wfk + ((((size_t)gi * g.nfold + sf) * 4) * 64 + lane_g) * NXT + t;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[e], ob[(size_t)e * 64 * NXT], c1, 0, 0, 0);
+                        for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(ob[(size_t)e * 64 * NXT], a2[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(a2[e], ob[(size_t)e * 64 * NXT], c1, 0, 0, 0);
                     }
                 }
                 const jx_ro_v4d cs = c0 + c1;
                 if (CT) {
-                    const int X = gi * 16 * NXT + 16 * t + li;
-                    if (X < g.nuse) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) s_row[(lk + 4 * r) * g.ldr + X] = cs[r] * cfv[tt][r];
-                    }
+                    for (int r = 0; r < 4; ++r) bv[tt][r] = cs[r];
                 } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (!JX_DBG(g, 4) || cs[r] == 1.234e300) Pb[(size_t)(lk + 4 * r) * (16 * NXT) + 16 * t + li] = cs[r];
                 }
             }
         }
+        if (CT) {
+            // ---- the group's share of the model at the data radii, m^T[d = 16 dt + lk + 4 r][w = li] += E (cfac . share) over the wave's tiles
+            //      in ascending order.  Between groups the sums wait in the wave's own part of the LDS area they are handed over in.
+            load_e(gi);
+            load_cf(gi);
+            jx_ro_v4d macc[JX_CT_NDT];
+#pragma unroll
+            for (int dt = 0; dt < JX_CT_NDT; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) macc[dt][r] = (gi > 0 && dt < g.ndt) ? s_m[((wv * g.ndt + dt) * 16 + lk + 4 * r) * 16 + li] : 0.0;
+#pragma unroll
+            for (int tt = 0; tt < NTT; ++tt)
+                if (wv + 4 * tt < NXT) {                         // (wave-uniform)
+                    // bv is D[x = lk + 4 r][w = li] of the row product: with its conversion factor, the B operand B[k = lk][w = li] of sub-step
+                    // r.  An output the data-radii matrix does not read is exactly 0 (its factor may be stale: 0 x NaN would poison the column)
+                    const int X0 = gi * 16 * NXT + 16 * (wv + 4 * tt) + lk;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) bv[tt][r] = (X0 + 4 * r < g.nuse) ? bv[tt][r] * cfv[tt][r] : 0.0;
+#pragma unroll
+                    for (int dt = 0; dt < JX_CT_NDT; ++dt)
+                        if (dt < g.ndt) {                        // (wave-uniform)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) macc[dt] = __builtin_amdgcn_mfma_f64_16x16x4f64(ev[tt][dt][r], bv[tt][r], macc[dt], 0, 0, 0);
+                        }
+                }
+#pragma unroll
+            for (int dt = 0; dt < JX_CT_NDT; ++dt)
+                if (dt < g.ndt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s_m[((wv * g.ndt + dt) * 16 + lk + 4 * r) * 16 + li] = macc[dt][r];
+                }
+        }
     }
     if (CT) {
-        // ---- the block's share of the model at the data radii: E (cfac . share), wave sums added in wave order
-        double* s_zc = sm_or + g.o_z;
-        const int nflux = g.nflux;
-        __syncthreads();
-        jx_row_dots_all(nflux, g.nrow, g.emat, g, s_row, s_zc, sm_or + g.o_E);
+        // ---- the block's share of the model at the data radii: the waves' [ndt][16 d][16 w] sums are added in wave order (the pair's
+        //      ordinates behind them in LDS stay untouched: no barrier in front of the row product)
         __syncthreads();
         double* __restrict__ Pmb = g.Pm + ((size_t)wt * g.npair + p) * 16 * (size_t)g.ldm;
-        for (int i = tid; i < 16 * nflux; i += 256) {
-            const int w = i / nflux, d = i - w * nflux;
+        for (int i = tid; i < 16 * g.nflux; i += 256) {
+            const int d = i >> 4, w = i & 15;
             double m = 0.0;
 #pragma unroll
-            for (int v = 0; v < 4; ++v) m += s_zc[((size_t)v * 16 + w) * (nflux + 1) + d];
+            for (int v = 0; v < 4; ++v) m += s_m[(v * g.ndt * 16 + d) * 16 + w];
             if (wb + w < g.n && !JX_DBG(g, 4)) Pmb[(size_t)w * g.ldm + d] = m;
         }
     }

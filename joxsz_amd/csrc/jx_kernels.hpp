@@ -618,7 +618,8 @@ jx_prep_kernel(JxDev c, const double* __restrict__ theta, int w0,
                                              ? (JX_SZ_PACK_DOUBLES(c) + (size_t)(c).N + (c).nt) : (JX_XR_PACK_DOUBLES(c) + 3 * (size_t)(c).nann + 2 * (size_t)(c).nband * (c).nann)) + 8)
 
 __global__ void __launch_bounds__(JX_W2_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
-jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __restrict__ base, double* __restrict__ cfac, double* __restrict__ pp_out, JxSm smv) {
+jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __restrict__ base, double* __restrict__ cfac, double* __restrict__ pp_out,
+                  int ncf /* conversion factors the launch's consumers read (<= nrow): the rest of a walker's row is not written */, JxSm smv) {
     JX_LDS_DECL;
     double* p = sm;
     double* red = sm + 20;
@@ -726,7 +727,7 @@ jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __r
     double part = 0.0;
     for (int k = tid; k < nt; k += nth) part += s_hw[k] * s_t[k];
     const double t0 = jx_block_sum(part, red);
-    for (int k = tid; k < c.nrow; k += nth) {
+    for (int k = tid; k < ncf; k += nth) {
         const double T = (k == 0) ? t0 : s_t[k - 1];
         cfac[(size_t)w * c.nrow + k] = jx_convert_tab(s_conv, s_conv + c.nconv, c.nconv, T) * p[P_CALIB];
     }

@@ -1070,6 +1070,23 @@ inline void abel_ordinate_layout(const std::vector<double>& r, double y_scale, i
                 }
 }
 
+// A operand of the contracted epilogue (jx_ordrow_kernel<NXT, true>): the data-radii matrix E [nflux][ld] against the transposed row
+// product, whose tile (g, t) leaves lane (lk, li) holding the outputs X = 16 (g NXT + t) + lk + 4 r, r = 0..3, of walker li; sub-step r
+// of the second product takes A[m = li][k = lk] = E[16 dt + li][X],
+//     Eop[((((g NXT + t) ndt + dt) 64 + 16 lk + li) 4 + r] = E[16 dt + li][16 (g NXT + t) + lk + 4 r],   ndt = ceil(nflux / 16)
+// (exact zeros for data radii >= nflux and outputs >= nuse): one 32-byte load per lane, tile and dt.
+inline void contract_operand_layout(const double* E, int nflux, int ld, int nuse, int NXT, int ng, std::vector<double>& Eop) {
+    const int ndt = (nflux + 15) / 16;
+    Eop.assign((size_t)ng * NXT * ndt * 256, 0.0);
+    for (int gt = 0; gt < ng * NXT; ++gt)
+        for (int dt = 0; dt < ndt; ++dt)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int r = 0; r < 4; ++r) {
+                    const int d = 16 * dt + (lane & 15), X = 16 * gt + (lane >> 4) + 4 * r;
+                    if (d < nflux && X < nuse) Eop[(((size_t)gt * ndt + dt) * 64 + lane) * 4 + r] = E[(size_t)d * ld + X];
+                }
+}
+
 // smallest even 2^a 3^b 5^c >= n
 inline int next_smooth_even(int n) {
     for (int m = std::max(2, n + (n & 1));; m += 2) {

@@ -226,6 +226,13 @@ int jxt_abel_ordinate_layout(const double* r, int n, double y_scale, int nS, int
     std::copy(o.begin(), o.end(), out);
     return 0;
 }
+// the data-radii matrix E [nflux][ld] as the A operand of the contracted epilogue: out [ng][NXT][ceil(nflux / 16)][64][4]
+int jxt_contract_operand_layout(const double* E, int nflux, int ld, int nuse, int NXT, int ng, double* out) {
+    std::vector<double> o;
+    jxt::contract_operand_layout(E, nflux, ld, nuse, NXT, ng, o);
+    std::copy(o.begin(), o.end(), out);
+    return 0;
+}
 
 // radices of the LDS transforms of the literal route for length n (jx_fft.hpp): passes, or 0 when the length is not 2^a 3^b 5^c
 int jxt_fft_radices(int n, int* radix /*[12]*/) { return jxt::fft_radices(n, radix, 12); }
