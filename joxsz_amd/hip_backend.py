@@ -276,7 +276,7 @@ class HipContext:
         return d
 
     def _truncation_warning(self, d):
-        """One line when the guard changed the tables or has little room left (jx_finalize, joxsz_hip.hip): what happened and
+        """One line when the guard changed the tables or has little room left (mix_guard, csrc/jx_host_mix.hpp): what happened and
         what it costs.  Stages 1 and 2 of the low-rank form cost about (4 + rank) and rank multiply-adds per map sample, so
         the step scales roughly with (4 + 2 rank) / (4 + 2 * 16) of the 16-term tables a smooth transfer function gets."""
         if self.conv != 'custom':

@@ -40,7 +40,7 @@ both sides on the CPU -- numpy's fp64 evaluation of the same chain stays below a
 macro step of 16 radii or data radius exceeds it by orders of magnitude.
 
 The layout.  ``SzChain.layout`` restates, from the same tables, which instance of the kernels the library picks for the problem
-(plan_mix and jx_finalize of csrc/joxsz_hip.hip): the outputs in use under JX_PRUNE_TOL, NXT, the output groups, the ordinate tiles,
+(plan_exact of csrc/jx_host_exact.hpp and data_radii_matrix of csrc/joxsz_hip.hip): the outputs in use under JX_PRUNE_TOL, NXT, the output groups, the ordinate tiles,
 pairs and fold steps.  The GPU tests hold the live context to it."""
 import ctypes
 import os
@@ -91,7 +91,7 @@ class SzChain:
         self.Wy, self.Nk = Wy, int(nk)
         xk = np.ascontiguousarray(pb.radius[S // 2:], dtype=np.float64)
         self.set_data(pb.flux_data, lib, xk)
-        # ---- the instance the library picks (plan_mix / jx_finalize)
+        # ---- the instance the library picks (plan_exact / data_radii_matrix)
         emax = np.abs(self.E).max()
         used = np.flatnonzero(np.abs(self.E).max(axis=0) > PRUNE_TOL * emax)
         nuse = max(1, int(used[-1]) + 1) if used.size else nrow
