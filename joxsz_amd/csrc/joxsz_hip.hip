@@ -212,8 +212,9 @@ static void launch_prep(jx_ctx* ctx, const Chunk& c, hipStream_t ps, double* pp_
     if (opt_str(ctx, "JOXSZ_P_STAMPS")) prep_stamps(ps, n, c.xr_split, dp);
 #endif
     const unsigned pgrid = c.xr_split ? 2u * (unsigned)n : (unsigned)n, pthr = c.xr_split ? 128u : (unsigned)JX_PREP_THREADS;
-    if (c.xr_split && ctx->prep_lean && ctx->prep_fastmath && pp_buf && sizeof(double) * JX_W2_LDS_DOUBLES(d) <= (size_t)19 * 1024 + 512) {
-        // the two-block form as two lean roles (same arithmetic, same bits; every table of a role in one batched copy into LDS)
+    if (c.xr_split && ctx->prep_lean && ctx->prep_fastmath && pp_buf && sizeof(double) * JX_W2_LDS_DOUBLES(d) <= (size_t)19 * 1024 + 512 &&
+        d.N <= JX_W2_RPL * JX_W2_THREADS && 3 * d.nann <= JX_W2_THREADS) {
+        // the two-block form as two lean roles (same arithmetic, same bits; every table of a role in one batched copy into LDS, a lane's radii in registers)
         hipLaunchKernelGGL(jx_walker2_kernel, dim3(pgrid), dim3(JX_W2_THREADS), sizeof(double) * JX_W2_LDS_DOUBLES(d), ps, dp, c.theta, c.w0, c.base, c.cfac, pp_buf, ncf, c.sm);
         return;
     }
@@ -760,9 +761,14 @@ static int walker_tables(jx_ctx* ctx, const std::vector<double>& r, const std::v
                 const std::vector<double> v = host_vec<double>(ctx, id);
                 pack.insert(pack.end(), v.begin(), v.end());
             }
+            pack.insert(pack.end(), 2 * (size_t)d.nann, 0.0);    // log x_r_ne | log x_r_T: filled on the device below
             if (pack.size() != JX_XR_PACK_DOUBLES(d)) { ctx->err = "X-ray table pack: size"; return JX_ERR_INVALID; }
             if ((rc = dev_put(ctx, pack.data(), pack.size(), &p))) return rc;
             d.xr_pack = p;
+            // the logarithms of the X-ray radii by the device's own table-driven function, once (the host's differ in the last bits)
+            hipLaunchKernelGGL(jx_xr_logr_kernel, dim3(1), dim3(64), 0, 0, d.fm_tab, p + JX_FM_TABLE_DOUBLES, p + pack.size() - 2 * (size_t)d.nann, 2 * d.nann);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipDeviceSynchronize());
         }
 #undef PUTD
 #undef PUTI

@@ -4,6 +4,7 @@
 //   jx_prep_kernel          theta -> parameter vector, priors, mass veto, pressure and T_SZ profiles,
 //                           Compton->mJy/beam factors, X-ray counts + Cash likelihood (every call with taps; pow() form; calc_integ)
 //   jx_walker2_kernel       the same work of the TIMED path as two lean roles per walker in one launch (same bits)
+//   jx_xr_logr_kernel       log of the X-ray radii for that kernel's X-ray role, once per context
 //   jx_abel_gemm_kernel     Abel integral, Compton-y scale and spline moments of a launch as one fp64 matrix-core product
 //   jx_abel_map_sym_kernel  FUSED gNFW profile -> Abel integral -> Compton y -> cubic spline -> S x S map (symmetric
 //   jx_abel_map_kernel      d_mat / any d_mat): the profile taps, the y_2d tap, the rocFFT sequence, the full-map measurement
@@ -48,6 +49,7 @@
 #define JX_PREP_THREADS 256
 #endif
 #define JX_TAIL_THREADS 256
+#define JX_W2_THREADS 128      // jx_walker2_kernel: two waves per block
 
 // semantic slots of the parameter vector (joxsz_amd/problem.py PAR_SLOTS)
 enum {
@@ -406,6 +408,147 @@ __device__ __forceinline__ void jx_xray_side(const JxDev& c, const JxXrTab& xt, 
     *xlike_out = xlike; *xbad_out = xbad;
 }
 
+// The same copy in 16-byte loads and stores (dst, src 16-byte aligned: the LDS carve and a pack's own allocation), with a hole in the source:
+// dst[0, n) <- src[0, split) | src[split + gap, gap + n); split and gap even.  Half the wave instructions for the same bytes.
+template <int U>
+__device__ __forceinline__ void jx_copy_batched16(double* __restrict__ dst, const double* __restrict__ src, int n, int split, int gap, int tid, int nth) {
+    const double2* __restrict__ s2 = reinterpret_cast<const double2*>(src);
+    double2* __restrict__ d2 = reinterpret_cast<double2*>(dst);
+    const int n2 = n >> 1, split2 = split >> 1, gap2 = gap >> 1;
+    for (int i0 = 0; i0 < n2; i0 += U * nth) {
+        double2 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int i = min(i0 + u * nth + tid, n2 - 1); v[u] = s2[i < split2 ? i : i + gap2]; }
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int i = i0 + u * nth + tid; if (i < n2) d2[i] = v[u]; }
+    }
+    if ((n & 1) && tid == 0) dst[n - 1] = src[(n - 1 < split) ? n - 1 : n - 1 + gap];
+}
+
+// The X-ray side of jx_walker2_kernel's X-ray role: jx_xray_side's log form without taps, every operation on the same operands in the same
+// order (the same bits), scheduled for a block of two waves.
+//   shell profiles  one code path per wave while 2 nann <= 64: wave 0 evaluates the density -- lanes [0, nann) at the n_e radii, lanes
+//                   [nann, 2 nann) at the T radii where the two differ -- and wave 1 the pressure at the T radii, at the same time (as
+//                   three lane groups of ONE wave, jx_xray_side's mapping, the three branches run one after the other); the logarithms of
+//                   the radii come with the pack (xt_lr: log x_r_ne | log x_r_T, jx_xr_logr_kernel)
+//   log T_X         its special cases and the interval of the temperature grid once per annulus, by the lane that forms T_X: log T_X takes
+//                   the pressure's place in s_T, and the interval's lower index (or -1 NaN, -2 at or below the grid, -3 at or above it) the
+//                   place of the second density in s_x, as an int per double -- a lane overwrites only what it alone has read; the
+//                   count-rate phase does the gathers, the two quotients and the two exp of jx_interp_clamped2 per (band, annulus)
+//   Cash sum        one barrier: each wave's verdict goes beside the terms, wave 0 adds the terms in jx_xray_side's order and thread 0 stores
+template <class M>
+__device__ __forceinline__ void jx_xray_side_lean(const JxDev& c, const JxXrTab& xt, const double* xt_lr, const double* p, const double* pl, const M& mt, int tid,
+                                                  double* s_x, double* s_ne, double* s_T, double* s_rate, double* s_term, int* redw,
+                                                  size_t w) {
+    constexpr int nth = JX_W2_THREADS;
+    const int nann = c.nann;
+    if (2 * nann <= 64) {
+        if (tid < 64) {
+            const int second = tid >= nann, k = second ? tid - nann : tid;
+            if (tid < 2 * nann) {
+                const double rn = xt.x_r_ne[k], rT = xt.x_r_T[k];
+                const double r = second ? rT : rn, lr = xt_lr[tid];
+                double v = 0.0;
+                if (!(second && rn == rT)) v = jx_ne_log(mt, p, pl, r, lr, c.ne_mode);
+                (second ? s_x : s_ne)[k] = v;
+            }
+        } else if (tid - 64 < nann) {
+            double xa;
+            s_T[tid - 64] = jx_press_log(mt, p, pl, xt_lr[nann + tid - 64], &xa) * mt.e(2.30258509299404568402 * p[P_LOGTR]);
+        }
+    } else {
+        // (jx_xray_side's mapping: 3 nann <= the block's threads where this kernel is launched)
+        const int grp = tid / nann, k = tid - grp * nann;
+        if (grp < 3) {
+            const double rn = xt.x_r_ne[k], r = xt.x_r_T[k];
+            if (grp == 0) s_ne[k] = jx_ne_log(mt, p, pl, rn, xt_lr[k], c.ne_mode);
+            else if (grp == 1) { double xa; s_T[k] = jx_press_log(mt, p, pl, xt_lr[nann + k], &xa) * mt.e(2.30258509299404568402 * p[P_LOGTR]); }
+            else s_x[k] = (rn == r) ? 0.0 : jx_ne_log(mt, p, pl, r, xt_lr[nann + k], c.ne_mode);
+        }
+    }
+    __syncthreads();
+    if (tid < nann) {
+        const double T = s_T[tid] / ((xt.x_r_ne[tid] == xt.x_r_T[tid]) ? s_ne[tid] : s_x[tid]);   // T_X
+        // the head of jx_interp_clamped2 on x = log T_X
+        const double x = mt.l(T);
+        const double* xp = xt.lnT;
+        const int n = c.ntab;
+        int lo;
+        if (x != x) lo = -1;
+        else if (x <= xp[0]) lo = -2;
+        else if (x >= xp[n - 1]) lo = -3;
+        else {
+            lo = (int)((x - xp[0]) * c.inv_dlnT);
+            lo = max(0, min(n - 2, lo));
+            while (lo > 0 && xp[lo] > x) --lo;
+            while (lo < n - 2 && xp[lo + 1] <= x) ++lo;
+        }
+        s_T[tid] = x; reinterpret_cast<int*>(s_x)[2 * tid] = lo;
+    }
+    __syncthreads();
+    JX_PSTAMP(c, 2);
+    const int nba = c.nband * nann;
+    for (int q = tid; q < nba; q += nth) {
+        const int b = q / nann, j = q - b * nann;
+        const double x = s_T[j];
+        const int lo = reinterpret_cast<const int*>(s_x)[2 * j], n = c.ntab;
+        const double* f0 = xt.lnrate + (size_t)b * 2 * n;
+        const double* f1 = f0 + n;
+        double i0, i1;
+        if (lo == -1) { i0 = x; i1 = x; }
+        else if (lo == -2) { i0 = f0[0]; i1 = f1[0]; }
+        else if (lo == -3) { i0 = f0[n - 1]; i1 = f1[n - 1]; }
+        else {
+            const double* xp = xt.lnT;
+            const int hi = lo + 1;
+            const double dx = xp[hi] - xp[lo], t = x - xp[lo];
+            i0 = (f0[hi] - f0[lo]) / dx * t + f0[lo];
+            i1 = (f1[hi] - f1[lo]) / dx * t + f1[lo];
+        }
+        const double z0 = mt.e(i0), z1 = mt.e(i1);
+        s_rate[q] = (z0 + (z1 - z0) * p[P_Z]) * s_ne[j] * s_ne[j];
+    }
+    __syncthreads();
+    JX_PSTAMP(c, 3);
+    int bad = 0;
+    for (int q = tid; q < nba; q += nth) {
+        const int b = q / nann, i = q - b * nann;
+        double proj = 0.0;
+        for (int j = 0; j < nann; ++j) proj += xt.projvols[i * nann + j] * s_rate[b * nann + j];
+        const double ae = xt.areascales[q] * xt.exposures[q];
+        const double model = proj * ae + xt.backrates[q] * xt.geomarea[i] * ae * p[P_BACKSCALE];
+        if (!(model > 0.0)) bad = 1;       // np.array(profs).min() > 0 fails (NaN included)
+        const double ct = xt.cts[q];
+        s_term[q] = (ct == ct) ? ct * mt.l(model) - model : 0.0;
+    }
+    JX_PSTAMP(c, 4);
+    const int wbad = __any(bad);
+    if ((tid & 63) == 0) redw[tid >> 6] = wbad;
+    __syncthreads();
+    JX_PSTAMP(c, 5);
+    if (tid < 64) {
+        double tot = 0.0;
+        for (int q0 = 0; q0 < nba; q0 += 64) {
+            double v = (q0 + tid < nba) ? s_term[q0 + tid] : 0.0;
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+            tot += v;
+        }
+        if (tid == 0) {
+            // cashLogLikelihood returns -inf for a non-finite sum; per band in the reference, a non-finite band makes the total non-finite as well
+            const int xbad = (redw[0] | redw[1]) || !(fabs(tot) <= 1.79769313486231570e308);
+            c.xr_out[2 * w] = tot; c.xr_out[2 * w + 1] = xbad ? 1.0 : 0.0;
+        }
+    }
+}
+
+// log of the X-ray radii, once per context (jx_finalize): the 2 nann doubles behind the tables of xr_pack from its x_r_ne | x_r_T, by the
+// function and the tables the per-walker kernels evaluate them with (the host's logarithm differs in the last bits)
+__global__ void jx_xr_logr_kernel(const double* __restrict__ fm_tab, const double* __restrict__ r, double* __restrict__ out, int n) {
+    JxFm t;
+    t.et = fm_tab; t.lt = fm_tab + JX_FM_EXP_N;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = jx_fm_log(t, r[i]);
+}
+
 // ------------------------------------------------------------------------------------
 // K0: per-walker scalar work.  One 256-thread block per walker.
 //   base  [W]  parprior + model prior + X-ray log-likelihood, or -inf when rejected
@@ -609,21 +752,27 @@ jx_prep_kernel(JxDev c, const double* __restrict__ theta, int w0,
 // block pays one trip to memory in front of its first barrier instead of one per phase (the count-rate tables stay in memory: two gathers
 // behind the temperature search, which runs on the LDS copy of the grid).
 //   sz_pack  [JX_FM_TABLE_DOUBLES + 2 N + nt + 2 nconv]    fm | r_pp | log r_pp | hw | conv_T | conv_v
-//   xr_pack  [JX_FM_TABLE_DOUBLES + 3 nann + ntab + nann^2 + 4 nband nann]    fm | x_r_ne | x_r_T | geomarea | lnT | projvols | areascales | exposures | backrates | cts
+//   xr_pack  [JX_FM_TABLE_DOUBLES + 5 nann + ntab + nann^2 + 4 nband nann]
+//            fm | x_r_ne | x_r_T | geomarea | lnT | projvols | areascales | exposures | backrates | cts | log x_r_ne | log x_r_T (jx_xr_logr_kernel)
+// The radii and their logarithms do not pass through LDS: a lane of the SZ-side role reads exactly its own (up to JX_W2_RPL each), so it
+// loads them from sz_pack into registers in the same burst as the table copy, and the copy leaves them out (fm | hw | conv_T | conv_v).
 // ------------------------------------------------------------------------------------
-#define JX_W2_THREADS 128
+#define JX_W2_RPL 6            // radii per lane the SZ-side role holds in registers: N <= JX_W2_RPL * JX_W2_THREADS
 #define JX_SZ_PACK_DOUBLES(c) ((size_t)JX_FM_TABLE_DOUBLES + 2 * (size_t)(c).N + (c).nt + 2 * (size_t)(c).nconv)
-#define JX_XR_PACK_DOUBLES(c) ((size_t)JX_FM_TABLE_DOUBLES + 3 * (size_t)(c).nann + (c).ntab + (size_t)(c).nann * (c).nann + 4 * (size_t)(c).nband * (c).nann)
-#define JX_W2_LDS_DOUBLES(c) (JX_LDS_HDR + ((JX_SZ_PACK_DOUBLES(c) + (size_t)(c).N + (c).nt) > (JX_XR_PACK_DOUBLES(c) + 3 * (size_t)(c).nann + 2 * (size_t)(c).nband * (c).nann) \
-                                             ? (JX_SZ_PACK_DOUBLES(c) + (size_t)(c).N + (c).nt) : (JX_XR_PACK_DOUBLES(c) + 3 * (size_t)(c).nann + 2 * (size_t)(c).nband * (c).nann)) + 8)
+#define JX_SZ_TAB_DOUBLES(c) ((size_t)JX_FM_TABLE_DOUBLES + (c).nt + 2 * (size_t)(c).nconv)      /* what of sz_pack an SZ-side block copies into LDS */
+#define JX_XR_PACK_DOUBLES(c) ((size_t)JX_FM_TABLE_DOUBLES + 5 * (size_t)(c).nann + (c).ntab + (size_t)(c).nann * (c).nann + 4 * (size_t)(c).nband * (c).nann)
+// (SZ-side: its tables, the mass profile [N], T_SZ [nt]; X-ray: its pack, n_e | P, then log T_X | n_e at the T radii, then the interval [nann] each, rates and Cash terms [nband nann] each)
+#define JX_W2_LDS_SZ(c) (JX_SZ_TAB_DOUBLES(c) + (size_t)(c).N + (c).nt)
+#define JX_W2_LDS_XR(c) (JX_XR_PACK_DOUBLES(c) + 3 * (size_t)(c).nann + 2 * (size_t)(c).nband * (c).nann)
+#define JX_W2_LDS_DOUBLES(c) (JX_LDS_HDR + (JX_W2_LDS_SZ(c) > JX_W2_LDS_XR(c) ? JX_W2_LDS_SZ(c) : JX_W2_LDS_XR(c)) + 8)
 
 __global__ void __launch_bounds__(JX_W2_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
 jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __restrict__ base, double* __restrict__ cfac, double* __restrict__ pp_out,
                   int ncf /* conversion factors the launch's consumers read (<= nrow): the rest of a walker's row is not written */, JxSm smv) {
     JX_LDS_DECL;
     double* p = sm;
-    double* red = sm + 20;
-    int& redi = *reinterpret_cast<int*>(sm + 28);
+    double* red = sm + 20;                                 // [4] the two sums of the SZ-side role's reduction round, per wave
+    int* redw = reinterpret_cast<int*>(sm + 24);           // [2] per-wave rejection bits (either role)
     const int nblk = (int)(gridDim.x >> 1);
     const bool xonly = (int)blockIdx.x >= nblk;
     const int w = xonly ? (int)blockIdx.x - nblk : (int)blockIdx.x, gw = w0 + w;
@@ -634,13 +783,14 @@ jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __r
     mt.t.et = s_pack; mt.t.lt = s_pack + JX_FM_EXP_N;
     if (xonly) {
         // ---- the X-ray side alone ----
-        jx_copy_batched<12>(s_pack, c.xr_pack, (int)JX_XR_PACK_DOUBLES(c), tid, nth);
+        jx_copy_batched16<6>(s_pack, c.xr_pack, (int)JX_XR_PACK_DOUBLES(c), 0, 0, tid, nth);
         jx_load_params(c, theta, gw, p, &smv);
         JX_PSTAMP(c, 1);
         const int nann = c.nann, nba = c.nband * c.nann;
         const double* t = s_pack + JX_FM_TABLE_DOUBLES;
         const JxXrTab xt{t, t + nann, t + 3 * nann, c.lnrate, t + 3 * nann + c.ntab, t + 3 * nann + c.ntab + nann * nann, t + 3 * nann + c.ntab + nann * nann + nba,
                          t + 3 * nann + c.ntab + nann * nann + 2 * nba, t + 2 * nann, t + 3 * nann + c.ntab + nann * nann + 3 * nba};
+        const double* s_lr = t + 3 * nann + c.ntab + nann * nann + 4 * nba;   // [2 nann] log x_r_ne | log x_r_T
         double* s_ne = s_pack + JX_XR_PACK_DOUBLES(c);
         double* s_T = s_ne + nann;
         double* s_x = s_T + nann;
@@ -648,28 +798,30 @@ jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __r
         double* s_term = s_rate + nba;
         double pl[11];
         jx_prof_consts(mt, p, c.ne_mode, pl);
-        const double pc[5] = {0, 1, 1, 0, 1};
-        double xlike = 0.0;
-        int xbad = 0;
-        jx_xray_side<false>(c, xt, p, pl, pc, mt, tid, nth, s_x, s_ne, s_T, s_rate, s_term, red, &redi, (size_t)w, nullptr, &xlike, &xbad);
-        if (tid == 0) { c.xr_out[2 * (size_t)w] = xlike; c.xr_out[2 * (size_t)w + 1] = xbad ? 1.0 : 0.0; }
+        jx_xray_side_lean(c, xt, s_lr, p, pl, mt, tid, s_x, s_ne, s_T, s_rate, s_term, redw, (size_t)w);
         JX_PSTAMP(c, 6);
         return;
     }
     // ---- everything but the X-ray side ----
     const int N = c.N, nt = c.nt;
-    const double* s_r = s_pack + JX_FM_TABLE_DOUBLES;      // [N]
-    const double* s_lr = s_r + N;                           // [N]
-    const double* s_hw = s_lr + N;                          // [nt]
+    const double* s_hw = s_pack + JX_FM_TABLE_DOUBLES;     // [nt]
     const double* s_conv = s_hw + nt;                       // [2 nconv]
-    double* s_m = s_pack + JX_SZ_PACK_DOUBLES(c);          // [N] mass profile
+    double* s_m = s_pack + JX_SZ_TAB_DOUBLES(c);           // [N] mass profile
     double* s_t = s_m + N;                                  // [nt] T_SZ on r_pp[:nt]
     const bool has_par = tid < c.npar;
     const int pk_kind = has_par ? c.par_kind[tid] : 0;
     const double pk_a = has_par ? (pk_kind == 1 ? c.par_mu[tid] : c.par_min[tid]) : 0.0;
     const double pk_b = has_par ? (pk_kind == 1 ? c.par_sigma[tid] : c.par_max[tid]) : 0.0;
     const double pk_ln = has_par ? c.par_lnorm[tid] : 0.0;
-    jx_copy_batched<20>(s_pack, c.sz_pack, (int)JX_SZ_PACK_DOUBLES(c), tid, nth);
+    // this lane's radii of the grid pass and their logarithms (slot u: radius min(tid + u nth, N - 1), the pass's own clamp)
+    double rq[JX_W2_RPL], lq[JX_W2_RPL];
+#pragma unroll
+    for (int u = 0; u < JX_W2_RPL; ++u) {
+        const int i = min(tid + u * nth, N - 1);
+        rq[u] = c.sz_pack[JX_FM_TABLE_DOUBLES + i];
+        lq[u] = c.sz_pack[JX_FM_TABLE_DOUBLES + N + i];
+    }
+    jx_copy_batched16<3>(s_pack, c.sz_pack, (int)JX_SZ_TAB_DOUBLES(c), JX_FM_TABLE_DOUBLES, 2 * N, tid, nth);
     jx_load_params(c, theta, gw, p, &smv);
     JX_PSTAMP(c, 1);
     double pl[11];
@@ -689,18 +841,20 @@ jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __r
         } else if (v < pk_a || v > pk_b) rej |= REJ_BOX;
         if (v != v) rej |= REJ_BOX;           // NaN parameter: reject (emcee cannot use NaN)
     }
-    const double parprior = jx_block_sum(pr, red);
+    // (the thread's prior term and its rejection bits wait in registers: nothing reads their block-wide values before the end)
     JX_PSTAMP(c, 2);
-    if (!(fabs(parprior) <= 1.79769313486231570e308)) rej |= REJ_BOX;     // joxsz_funcs.py:519-520
     if (tid == 0 && p[P_LOGRC] > p[P_LOGRS]) rej |= REJ_RCRS;             // model prior: r_c <= r_s (joxsz_funcs.py:397-407; 10^x is monotonic)
     // one pass over the radial grid, two radii per trip (jx_prep_kernel's arithmetic)
     const bool veto = c.exclude_unphy_mass != 0;
     const int mode_ = c.ne_mode;
     const size_t ppo = (size_t)w * (c.pp_ld ? c.pp_ld : N);
-    for (int i = tid; i < N; i += 2 * nth) {
+#pragma unroll
+    for (int u = 0; u < JX_W2_RPL; u += 2) {
+        const int i = tid + u * nth;
+        if (i >= N) break;
         const int i2 = min(i + nth, N - 1);
         const bool two = i + nth < N;
-        const double ra = s_r[i], rb = s_r[i2], lra = s_lr[i], lrb = s_lr[i2];
+        const double ra = rq[u], rb = rq[u + 1], lra = lq[u], lrb = lq[u + 1];
         double xaa, xab;
         const double pa = jx_press_log(mt, p, pl, lra, &xaa), pb = jx_press_log(mt, p, pl, lrb, &xab);
         const double ia = jx_inv_ne_log(mt, p, pl, ra, lra, mode_), ib = jx_inv_ne_log(mt, p, pl, rb, lrb, mode_);      // 1 / n_e
@@ -726,14 +880,27 @@ jx_walker2_kernel(JxDev c, const double* __restrict__ theta, int w0, double* __r
     // h(0), conversion factors (joxsz_funcs.py:470-473)
     double part = 0.0;
     for (int k = tid; k < nt; k += nth) part += s_hw[k] * s_t[k];
-    const double t0 = jx_block_sum(part, red);
+    // ONE reduction round for the prior sum, the h(0) sum and the rejection bits: the sums by jx_block_sum's shuffle tree and wave order (the
+    // same bits), one barrier for all three (red and redw have no earlier reader)
+    for (int off = 32; off > 0; off >>= 1) {
+        pr += __shfl_down(pr, off, 64);
+        part += __shfl_down(part, off, 64);
+        rej |= __shfl_down(rej, off, 64);
+    }
+    if ((tid & 63) == 0) { red[tid >> 6] = pr; red[2 + (tid >> 6)] = part; redw[tid >> 6] = rej; }
+    __syncthreads();
+    double parprior = 0.0, t0 = 0.0;
+    for (int k = 0; k < JX_W2_THREADS / 64; ++k) { parprior += red[k]; t0 += red[2 + k]; }
     for (int k = tid; k < ncf; k += nth) {
         const double T = (k == 0) ? t0 : s_t[k - 1];
         cfac[(size_t)w * c.nrow + k] = jx_convert_tab(s_conv, s_conv + c.nconv, c.nconv, T) * p[P_CALIB];
     }
     JX_PSTAMP(c, 5);
-    const int rejall = jx_block_or(rej, &redi);
-    if (tid == 0) base[w] = (rejall != 0) ? -INFINITY : (parprior + 0.0);   // (the X-ray term arrives from the other block: the tail adds the two)
+    if (tid == 0) {
+        int rejall = redw[0] | redw[1];
+        if (!(fabs(parprior) <= 1.79769313486231570e308)) rejall |= REJ_BOX;     // joxsz_funcs.py:519-520
+        base[w] = (rejall != 0) ? -INFINITY : (parprior + 0.0);   // (the X-ray term arrives from the other block: the tail adds the two)
+    }
     JX_PSTAMP(c, 6);
 }
 
