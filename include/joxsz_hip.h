@@ -76,7 +76,12 @@ typedef struct jx_config {
                                * round 4 (16 singular terms, a sub-grid of map samples; measured by its guard, jx_get_truncation): 1 = fp32 spline arrays, every sum in
                                * fp64 (|delta chi^2/2| ~1e-6); 2 = fp32 arithmetic in stage 1 (packed fp32 FMAs) and stage 2 (fp32 matrix cores), K slices added in fp64:
                                * |delta chi^2/2| 2e-5 at 512^2, 1e-4 at 1024^2 ABSOLUTE -- inside north_star's relative 1e-6 only because the log-posterior is ~1e4;
-                               * jx_audit measures it on the caller's walkers */
+                               * jx_audit measures it on the caller's walkers.  3 = the exact form with its two big products (ordinates, row) on the fp32
+                               * matrix cores ('f32x'): operators rounded once to fp32, fp32 accumulation inside a wave's chains, everything per walker and everything
+                               * behind a pair's share of the row in fp64; held to a derived rounding bound (tests/sz_chain_f32.py).  One semantic difference: a
+                               * walker whose pressure profile is not finite or exceeds the range guard T (jx_get_exact_info out[7] = log2 T >= 32) gets -inf where
+                               * f64 would return a log-posterior of about -1e30 or below.  Exact form only: conv_mode 1, JOXSZ_MIX_FORM other than exact,
+                               * JOXSZ_X_PAIRWISE=0, a problem without the exact form and the operator route are refused with JX_ERR_UNSUPPORTED */
     int32_t calc_integ;       /* SZ_data.calc_integ: integrated-Compton term (joxsz_funcs.py:480-484, joxsz_main.py:65) */
     int32_t reserved1;        /* keeps the doubles 8-byte aligned; must be 0                   */
     double step;              /* arcsec                                   (joxsz_main.py:21)   */
@@ -349,7 +354,9 @@ int  jx_get_conv_layout(jx_ctx* ctx, int32_t out[12]);
  * for -- and out[1] < out[2]: where the partial would not be smaller than the row, as on maps of 32 pixels, nothing is gained), doubles per
  * walker of a contracted partial, doubles per walker and pair of a partial row, form of the LAST launch of this context (1 contracted, 0
  * partial rows, -1 none yet), 0 (the data-radii matrix of the contracted epilogue is never in LDS: it is read in operand order through the
- * caches), bytes of LDS per block of the row product of calls without those taps, 0, 0}.  JX_ERR_UNSUPPORTED unless the exact form is in use. */
+ * caches), bytes of LDS per block of the row product of calls without those taps, arithmetic of the two big products (0 f64, 1 fp32:
+ * jx_config.dtype 3), log2 of the range guard T on the pressure profile of a dtype-3 context (0 otherwise)}.  JX_ERR_UNSUPPORTED unless the
+ * exact form is in use. */
 int  jx_get_exact_info(jx_ctx* ctx, int32_t out[8]);
 /* Which map samples stage 1 of the low-rank form evaluates: out = {distinct rows (= columns) of the map quadrant NU; rows stage 1
  * evaluates; full resolution below this many pixels from the axis; every second row up to here (u1), every fourth up to 2 u1, every eighth beyond; interpolation

@@ -412,7 +412,7 @@ int jx_create(const jx_config* cfg, jx_ctx** out) {
     if (c.N < c.S - c.S / 2) return JX_ERR_INVALID;       // r_pp[:nrow-1] must exist (joxsz_funcs.py:469)
     if (!(c.step > 0) || !(c.kpc_as > 0) || !(c.m_e > 0) || !(c.sigma_T > 0) || !(c.kpc_cm > 0)) return JX_ERR_INVALID;
     if (c.nann > 64 || c.nband > 64 || c.N > 4096 || c.S > 4096) return JX_ERR_UNSUPPORTED;
-    if (c.dtype < 0 || c.dtype > 2) return JX_ERR_INVALID;
+    if (c.dtype < 0 || c.dtype > 3) return JX_ERR_INVALID;
     if (c.calc_integ && !(c.integ_sig > 0)) return JX_ERR_INVALID;
 
     int ndev = 0;
@@ -526,8 +526,11 @@ static int parse_options(jx_ctx* ctx, int* want_out, int* chunk_out) {
     ctx->op_narrow = opt_str(ctx, "JOXSZ_OP_NARROW") != nullptr;
     if (const char* e = opt_str(ctx, "JOXSZ_SIDE_STREAM")) ctx->side_on = atoi(e) != 0;
     if (const char* e = opt_str(ctx, "JOXSZ_SIDE_FORK")) ctx->side_fork = atoi(e) != 0;
-    ctx->f32 = c.dtype >= 1;
+    ctx->f32 = c.dtype == 1 || c.dtype == 2;
     ctx->f32c = c.dtype == 2;
+    ctx->f32x = c.dtype == 3;
+    if (ctx->f32x && want == 1) { ctx->err = "dtype 3 (f32x) is the exact form with fp32 products: the rocFFT sequence (conv = rocfft) is f64 only"; return JX_ERR_UNSUPPORTED; }
+    if (ctx->f32x && !ctx->exact.pairwise) { ctx->err = "dtype 3 (f32x): JOXSZ_X_PAIRWISE=0 selects the reference kernels of the exact form, which are f64 only"; return JX_ERR_UNSUPPORTED; }
     if (ctx->f32 && !ctx->abel_gemm) { ctx->err = "dtype f32 takes its spline arrays from the matrix product only (JOXSZ_ABEL_GEMM=0 is an f64 setting)"; return JX_ERR_UNSUPPORTED; }
 
     int chunk = c.max_batch > 0 ? c.max_batch : 1024;
@@ -627,6 +630,13 @@ static int choose_back_end(jx_ctx* ctx, int want, const std::vector<double>& r, 
     ctx->conv_mode = planned ? 2 : 1;
     if (ctx->f32 && ctx->conv_mode != 2) {                       // never silently fall back to the fp64 arithmetic
         ctx->err = "dtype f32 is available on the contracted route only" + (why.empty() ? std::string() : " (" + why + ")");
+        return JX_ERR_UNSUPPORTED;
+    }
+    if (ctx->f32x && !xb.ok) {                                    // dtype 3 is the exact form or nothing
+        const char* e = opt_str(ctx, "JOXSZ_MIX_FORM");
+        if (planned && e && strcmp(e, "exact")) ctx->err = std::string("dtype 3 (f32x) is the exact form with fp32 products: JOXSZ_MIX_FORM=") + e + " selects a contracted form (dtypes 1 and 2 run there)";
+        else if (planned) ctx->err = "dtype 3 (f32x): the exact form is not taken on this problem (the outputs the data-radii spline reads do not fit the tail's LDS)";
+        else ctx->err = "dtype 3 (f32x): the exact form does not exist on this problem" + (why.empty() ? std::string() : " (" + why + ")");
         return JX_ERR_UNSUPPORTED;
     }
     if (ctx->f32c && mixb.form != 0) {
@@ -1250,6 +1260,7 @@ extern "C" {
 int jx_set_route(jx_ctx* ctx, int route) {
     if (!ctx || (route != JX_ROUTE_MAP && route != JX_ROUTE_OPERATOR)) return JX_ERR_INVALID;
     if (!ctx->finalized) { ctx->err = "jx_set_route before jx_finalize"; return JX_ERR_STATE; }
+    if (route == JX_ROUTE_OPERATOR && ctx->f32x) { ctx->err = "dtype 3 (f32x): the operator route is built from and run in f64; use an f64 context for it"; return JX_ERR_UNSUPPORTED; }
     HIPCHK(ctx, hipSetDevice(ctx->cfg.device));
     if (route == JX_ROUTE_OPERATOR && !ctx->d_G) {
         const int rc = build_operator(ctx);
@@ -1566,7 +1577,7 @@ int jx_get_exact_info(jx_ctx* ctx, int32_t out[8]) {
     const bool ct = m.contracted();
     out[0] = ct ? 1 : 0; out[1] = m.ldm; out[2] = 16 * m.nxt * m.ng_use; out[3] = m.last_ct;
     out[4] = 0; out[5] = (int32_t)(sizeof(double) * (ct ? (size_t)JX_ORD_CT_LDS_DOUBLES(m.ndt) : (size_t)JX_ORD_LDS_DOUBLES));
-    out[6] = out[7] = 0;
+    out[6] = m.f32x ? 1 : 0; out[7] = m.f32x ? m.t_log2 : 0;
     return JX_OK;
 }
 
@@ -1578,7 +1589,7 @@ int jx_debug_workspace(jx_ctx* ctx, int which, void** dev, int32_t geom[4]) {
     if (ctx->exact.ready) {
         const ExactBack& x = ctx->exact;
         if (which == 6) { *dev = x.y; geom[0] = 1; geom[1] = (int)x.tW; geom[2] = x.Nkp; geom[3] = 8; return JX_OK; }
-        if (which == 7) { *dev = x.Opk; geom[0] = x.ng * (x.Nkp / 16) * 4; geom[1] = 64; geom[2] = x.nxt; geom[3] = 8; return JX_OK; }
+        if (which == 7) { *dev = x.f32x ? (void*)x.Opk32 : (void*)x.Opk; geom[0] = x.ng * (x.Nkp / 16) * 4; geom[1] = 64; geom[2] = x.nxt; geom[3] = x.f32x ? 4 : 8; return JX_OK; }
         if (which == 0 && ctx->d_img) { *dev = ctx->d_img; geom[0] = ctx->chunk; geom[1] = ctx->d.q_nb; geom[2] = (int)ctx->d.img_ld; geom[3] = 8; return JX_OK; }
         ctx->err = "exact form: work buffers 6 (ordinates [1][tW][Nkp]) and 7 (row operator) -- and 0 after a y_2d tap -- exist; the others belong to the contracted forms";
         return JX_ERR_UNSUPPORTED;

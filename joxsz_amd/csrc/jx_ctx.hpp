@@ -95,6 +95,11 @@ struct ExactBack {
     bool ct_ok = false;                // the contracted epilogue fits this problem (at most JX_CT_NDT tiles of data radii, fewer data radii than outputs)
     int ldm = 0, ndt = 0, last_ct = -1;   // its geometry (JxRowOp); form of the last launch (-1: none yet)
     double *Pm = nullptr, *Eop = nullptr;   // contracted partials [tW / 16][npair][16][ldm]; data-radii matrix as an operand [ng_use][nxt][ndt][64][4]
+    // fp32 products (jx_config.dtype 3): the three operators rounded once to fp32 IN PLACE of the fp64 ones (Wfk, Typ, Opk stay null), Eop in the
+    // fp32 instruction's output order, and the range guard T = 2^t_log2 on the profile (plan_exact)
+    bool f32x = false;
+    float *Wfk32 = nullptr, *Typ32 = nullptr, *Opk32 = nullptr;
+    int t_log2 = 0;
     long long tW = 0;
     JxRowOp ro{};                      // what every launch's kernel argument shares (exact_setup); run_exact adds the launch's own fields to a copy
     std::vector<void*> allocs;
@@ -162,6 +167,7 @@ struct jx_ctx {
     int ag_narrow = -1;                // JOXSZ_AG_NARROW: 16-walker blocks of the spline-array product for every launch (1) / never (0)
     bool f32 = false;                  // jx_config.dtype >= 1: fp32 spline arrays, fp32 evaluation of the map samples
     bool f32c = false;                 // jx_config.dtype == 2: fp32 arithmetic in stage 1 and stage 2 as well (packed fp32 FMAs, fp32 matrix cores)
+    bool f32x = false;                 // jx_config.dtype == 3: the exact form with its two big products on the fp32 matrix cores (neither f32 nor f32c is set)
 
     ExactBack exact;                   // conv_mode 2, default
     MixBack mix;                       // conv_mode 2, JOXSZ_MIX_FORM=legacy|lowrank|full (and every f32 context)
@@ -369,7 +375,7 @@ static int choose_form(const jx_ctx* ctx) {
         else if (!strcmp(e, "legacy")) form = JX_FORM_LEGACY; else if (!strcmp(e, "exact")) form = JX_FORM_EXACT;
     }
     if (form != JX_FORM_EXACT) return form;
-    if (ctx->f32) return JX_FORM_LEGACY;                         // (the fp32 variants exist on the forms of rounds 3-4)
+    if (ctx->f32) return JX_FORM_LEGACY;                         // (the fp32 variants 1 and 2 exist on the forms of rounds 3-4; dtype 3 is the exact form's own)
     // (the row of 16 walkers and the eight waves' partial tiles have to fit the LDS of the row product: data radii reaching
     //  across a very large map go to the contracted forms)
     const int nrow = ctx->nrow, nuse0 = std::min(ctx->prune ? std::max(1, ctx->nrow_use) : nrow, nrow);

@@ -17,6 +17,7 @@
 //                           take every fourth 16-radius step of the k-range each, straight from memory (no LDS staging, no barrier
 //                           in the loop), and meet in LDS.  The block then multiplies ITS 32 ordinates into the row operator --
 //                           a partial row [16][outputs] per pair -- so the ordinates never have to be read back.
+//   jx_ordrow32_kernel      the same block with its two big products on v_mfma_f32_16x16x4_f32 (jx_config.dtype 3; described at the kernel)
 //   jx_rowsum_tail_kernel   adds a walker tile's partial rows in pair order, then conversion factors, the not-a-knot spline to the
 //                           data radii (a constant nflux x nrow matrix), chi^2, total, and -- inside jx_sample -- the acceptance
 //                           of the stretch move.  One block per 16 walkers.
@@ -442,6 +443,241 @@ jx_ordrow_kernel(JxRowOp g) {
         }
     }
     JX_STAMP(g, 4);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same block with its two big products in fp32 (jx_config.dtype 3, 'f32x'): v_mfma_f32_16x16x4_f32, exact fp32 -- bit for bit an fmaf
+// chain in k order.  Decomposition, grid, LDS, fold, XCD map and every fp64 step around the two products are those of jx_ordrow_kernel;
+// the operators are the same tables rounded once to fp32 in the same operand orders (JxRowOp32: a lane loads 16 bytes where it loaded 32).
+//   ordinate product   pp rounded to nearest fp32 as it is loaded; fp32 accumulation inside a wave's chains; what leaves a wave (two chains
+//                      per tile, four waves) is converted to fp64 and added in fp64 in jx_ordrow_kernel's order; the ordinates stored for
+//                      calls with taps are those fp64 sums
+//   row product        the pair's 32 ordinates rounded once to fp32; row product and folded tile's share in fp32 registers (two chains:
+//                      lower tile | upper tile, then the fold steps), converted to fp64 and added before the conversion factor meets them;
+//                      the data-radii product E (cfac . share), Pm, P and the tails stay fp64
+// The A / B maps of the fp32 instruction are those of v_mfma_f64_16x16x4 (A[l & 15][k = l >> 4]); the C / D map is not: register r of lane l
+// is D[4 (l >> 4) + r][l & 15] (f64: D[(l >> 4) + 4 r][l & 15]).  So the transposed row product hands register r of a lane to the E product
+// as output 16 tile + 4 lk + r: Eop comes in a second permutation (jxt::contract_operand_layout, map 1), the conversion factors and the
+// in-use mask follow the same map (the four factors of a lane are contiguous), and the partial-row store and the waves' hand-over through
+// LDS index walker 4 lk + r.
+// Range guard (JxRowOp32::T, a power of two derived in plan_exact from the absolute row sums of the fp32 tables: no fp32 partial sum can
+// overflow while max |pp| <= T): an operand of the profile that is not finite or lies beyond T is replaced by 0 -- the walker's column
+// stays finite and touches nobody else's -- and the walker's base becomes -inf by a plain store (several lanes and blocks may store the same
+// value), so both tails return -inf.  No fp32 inf can reach the row, where inf - inf would be a NaN that nansum semantics drop.
+// ------------------------------------------------------------------------------------------------------------------
+typedef float jx_ro_v4f __attribute__((ext_vector_type(4)));
+
+struct JxRowOp32 {
+    const float* Wfk;              // JxRowOp::Wfk, Opk, Typ rounded to fp32 (a nonzero entry below FLT_MIN in magnitude: 0), same layouts
+    const float* Opk;
+    const float* Typ;
+    double T;                      // range guard: |pp| beyond it (or not finite) rejects the walker
+    double* base;                  // [n] priors of the launch's walkers (per-walker kernel): -inf for a walker the guard rejects
+};
+
+template <int NXT, bool CT = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+jx_ordrow32_kernel(JxRowOp g, JxRowOp32 h) {
+    extern __shared__ __attribute__((aligned(16))) double sm_or32[];
+    const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntw = (g.n + 15) >> 4;
+    const int id = blockIdx.x, xcd = id & 7, jj = id >> 3;
+    const int p = jj % g.npair, wt = (jj / g.npair) * 8 + xcd;
+    if (wt >= ntw) return;
+    const int wb = wt * 16;
+    const int q = 2 * g.npair - 1 - p;                          // the pair's upper tile (may lie beyond the last: then p alone)
+    const bool hasq = q < g.nS;
+    double* s1 = sm_or32;                                       // [4][2][16 ordinates][16 walkers]
+    double* s_yt = sm_or32 + 4 * 2 * 256;                       // [16][36]
+
+    // ---- ordinate product, steps s = p + wv, p + wv + 4, ... of 16 radii
+    const int wq = min(wb + li, g.n - 1);                       // (a walker beyond the launch repeats the last: finite work, never stored)
+    const double* __restrict__ ppl = g.pp + (size_t)wq * g.ldpp + 4 * lk;
+    const float* __restrict__ tb = h.Typ + (size_t)lane * 4;
+    const double T = h.T;
+    bool bad = false;                                           // this lane met an operand of its walker outside the guard
+    auto load_a = [&](int s) -> jx_ro_v4d { return *reinterpret_cast<const jx_ro_v4d*>(ppl + 16 * s); };   // (rows padded with zeros to 16 nSj)
+    auto round_a = [&](const jx_ro_v4d& a) -> jx_ro_v4f {       // range guard, then round to nearest
+        jx_ro_v4f f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const bool ok = fabs(a[e]) <= T; bad |= !ok; f[e] = ok ? (float)a[e] : 0.0f; }
+        return f;
+    };
+    auto load_b = [&](int s, int t) -> jx_ro_v4f { return *reinterpret_cast<const jx_ro_v4f*>(tb + ((size_t)s * g.nS + t) * 256); };
+    jx_ro_v4f ap[2], aq[2];                                     // two chains per tile (sub-steps e and e + 2 share one)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) { ap[e] = jx_ro_v4f{0.0f, 0.0f, 0.0f, 0.0f}; aq[e] = jx_ro_v4f{0.0f, 0.0f, 0.0f, 0.0f}; }
+    {
+        int s = p + wv;
+        jx_ro_v4d a0, a1;
+        jx_ro_v4f bp0, bq0, bp1, bq1;
+        const int tq = hasq ? q : p;                            // (no upper tile: its loads repeat the lower one's, its products are skipped)
+        if (s < g.nSj) { a0 = load_a(s); bp0 = load_b(s, p); bq0 = load_b(s, tq); }
+        for (; s < g.nSj; s += 8) {
+            const int s1n = s + 4, s2n = s + 8;
+            if (s1n < g.nSj) { a1 = load_a(s1n); bp1 = load_b(s1n, p); bq1 = load_b(s1n, tq); }
+            {
+                const jx_ro_v4f f = round_a(a0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ap[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[e], bp0[e], ap[e & 1], 0, 0, 0);
+                if (hasq && s >= q) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) aq[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[e], bq0[e], aq[e & 1], 0, 0, 0);
+                }
+            }
+            if (s1n < g.nSj) {
+                if (s2n < g.nSj) { a0 = load_a(s2n); bp0 = load_b(s2n, p); bq0 = load_b(s2n, tq); }
+                const jx_ro_v4f f = round_a(a1);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ap[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[e], bp1[e], ap[e & 1], 0, 0, 0);
+                if (hasq && s1n >= q) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) aq[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[e], bq1[e], aq[e & 1], 0, 0, 0);
+                }
+            }
+        }
+    }
+    {
+        // register r of a lane is D[walker 4 lk + r][ordinate li]: the two chains added in fp64, one 32-byte store per tile
+        jx_ro_v4d yp, yq;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { yp[r] = (double)ap[0][r] + (double)ap[1][r]; yq[r] = (double)aq[0][r] + (double)aq[1][r]; }
+        *reinterpret_cast<jx_ro_v4d*>(s1 + ((wv * 2 + 0) * 16 + li) * 16 + 4 * lk) = yp;
+        *reinterpret_cast<jx_ro_v4d*>(s1 + ((wv * 2 + 1) * 16 + li) * 16 + 4 * lk) = yq;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 512; idx += 256) {
+        const int t = idx >> 8, cc = (idx >> 4) & 15, w = idx & 15;
+        const double v = ((s1[((0 * 2 + t) * 16 + cc) * 16 + w] + s1[((1 * 2 + t) * 16 + cc) * 16 + w]) + s1[((2 * 2 + t) * 16 + cc) * 16 + w]) + s1[((3 * 2 + t) * 16 + cc) * 16 + w];
+        s_yt[w * 36 + 16 * t + cc] = v;
+        const int tile = t ? q : p;
+        if (g.y && tile < g.nS && wb + w < g.n) g.y[(size_t)(wb + w) * g.ldy + 16 * tile + cc] = v;
+    }
+    __syncthreads();
+
+    // ---- this pair's share of the row product; wave v owns the output tiles v, v + 4
+    jx_ro_v4f yp, yq;                                           // the pair's 32 ordinates, rounded once
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { yp[e] = (float)s_yt[li * 36 + 4 * lk + e]; yq[e] = (float)s_yt[li * 36 + 16 + 4 * lk + e]; }
+    constexpr int NTT = (NXT + 3) / 4;
+    int lane_g = lane;                                          // (as in jx_ordrow_kernel: made opaque per group in the contracted form)
+    double* s_m = sm_or32;                                      // contracted form: [4][ndt][16][16] wave sums (the reduction area is dead behind the barrier above)
+    for (int gi = 0; gi < g.ng; ++gi) {
+#ifdef __HIP_DEVICE_COMPILE__
+        if (CT) asm volatile("" : "+v"(lane_g));
+#endif
+        float bpv[NTT][4], bqv[NTT][4];
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) {
+            const int t = min(wv + 4 * tt, NXT - 1);
+            const float* __restrict__ ob = h.Opk + ((size_t)gi * g.nS * 256 + lane_g) * NXT + t;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                bpv[tt][e] = ob[((size_t)p * 4 + e) * 64 * NXT];
+                bqv[tt][e] = ob[((size_t)(hasq ? q : p) * 4 + e) * 64 * NXT];
+            }
+        }
+        double bv[NTT][4];
+        const bool fold = p < g.nfold;
+        jx_ro_v4f af = jx_ro_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+        float bfv[NTT][4];
+        if (fold) {
+            af = round_a(load_a(g.s0f + p));
+#pragma unroll
+            for (int tt = 0; tt < NTT; ++tt) {
+                const int t = min(wv + 4 * tt, NXT - 1);
+                const float* __restrict__ ob = h.Wfk + ((((size_t)gi * g.nfold + p) * 4) * 64 + lane_g) * NXT + t;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bfv[tt][e] = ob[(size_t)e * 64 * NXT];
+            }
+        }
+        double* __restrict__ Pb = g.P + (((size_t)wt * g.npair + p) * g.ng + gi) * (size_t)(256 * NXT);
+#pragma unroll
+        for (int tt = 0; tt < NTT; ++tt) {
+            const int t = wv + 4 * tt;
+            if (t < NXT) {                                       // (wave-uniform)
+                jx_ro_v4f c0 = jx_ro_v4f{0.0f, 0.0f, 0.0f, 0.0f}, c1 = jx_ro_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) c0 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(bpv[tt][e], yp[e], c0, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(yp[e], bpv[tt][e], c0, 0, 0, 0);
+                if (hasq) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(bqv[tt][e], yq[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(yq[e], bqv[tt][e], c1, 0, 0, 0);
+                }
+                if (fold) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(bfv[tt][e], af[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], bfv[tt][e], c1, 0, 0, 0);
+                    for (int sf = p + g.npair; sf < g.nfold; sf += g.npair) {        // (more macro steps than pairs: short grids only)
+                        const jx_ro_v4f a2 = round_a(load_a(g.s0f + sf));
+                        const float* __restrict__ ob = h.Wfk + ((((size_t)gi * g.nfold + sf) * 4) * 64 + lane_g) * NXT + t;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(ob[(size_t)e * 64 * NXT], a2[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(a2[e], ob[(size_t)e * 64 * NXT], c1, 0, 0, 0);
+                    }
+                }
+                // fp64 from here on.  Plain: D[walker 4 lk + r][output li]; transposed: D[output 4 lk + r][walker li]
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double cs = (double)c0[r] + (double)c1[r];
+                    if (CT) bv[tt][r] = cs;
+                    else Pb[(size_t)(4 * lk + r) * (16 * NXT) + 16 * t + li] = cs;
+                }
+            }
+        }
+        if (CT) {
+            // ---- the group's share of the model at the data radii on v_mfma_f64_16x16x4, m^T[d = 16 dt + lk + 4 r][w = li] += E (cfac . share):
+            //      sub-step r takes B[k = lk][w = li] = cfac[w][X] share[X][w], X = 16 tile + 4 lk + r, against A[d = li][k = lk] = E[16 dt + li][X]
+            jx_ro_v4d ev[NTT][JX_CT_NDT];
+            double cfv[NTT][4];
+#pragma unroll
+            for (int tt = 0; tt < NTT; ++tt) {
+                const int t = min(wv + 4 * tt, NXT - 1);
+#pragma unroll
+                for (int dt = 0; dt < JX_CT_NDT; ++dt)
+                    ev[tt][dt] = *reinterpret_cast<const jx_ro_v4d*>(g.Eop + ((((size_t)gi * NXT + t) * g.ndt + min(dt, g.ndt - 1)) * 64 + lane_g) * 4);
+                const int X0 = gi * 16 * NXT + 16 * t + 4 * lk;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) cfv[tt][r] = g.cfac[(size_t)wq * g.nrow + min(X0 + r, g.nrow - 1)];
+            }
+            jx_ro_v4d macc[JX_CT_NDT];
+#pragma unroll
+            for (int dt = 0; dt < JX_CT_NDT; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) macc[dt][r] = (gi > 0 && dt < g.ndt) ? s_m[((wv * g.ndt + dt) * 16 + lk + 4 * r) * 16 + li] : 0.0;
+#pragma unroll
+            for (int tt = 0; tt < NTT; ++tt)
+                if (wv + 4 * tt < NXT) {                         // (wave-uniform)
+                    // An output the data-radii matrix does not read is exactly 0 (its factor may be stale: 0 x NaN would poison the column)
+                    const int X0 = gi * 16 * NXT + 16 * (wv + 4 * tt) + 4 * lk;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) bv[tt][r] = (X0 + r < g.nuse) ? bv[tt][r] * cfv[tt][r] : 0.0;
+#pragma unroll
+                    for (int dt = 0; dt < JX_CT_NDT; ++dt)
+                        if (dt < g.ndt) {                        // (wave-uniform)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) macc[dt] = __builtin_amdgcn_mfma_f64_16x16x4f64(ev[tt][dt][r], bv[tt][r], macc[dt], 0, 0, 0);
+                        }
+                }
+#pragma unroll
+            for (int dt = 0; dt < JX_CT_NDT; ++dt)
+                if (dt < g.ndt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s_m[((wv * g.ndt + dt) * 16 + lk + 4 * r) * 16 + li] = macc[dt][r];
+                }
+        }
+    }
+    if (bad && wb + li < g.n) h.base[wb + li] = -INFINITY;
+    if (CT) {
+        // ---- the block's share of the model at the data radii: the waves' [ndt][16 d][16 w] sums added in wave order
+        __syncthreads();
+        double* __restrict__ Pmb = g.Pm + ((size_t)wt * g.npair + p) * 16 * (size_t)g.ldm;
+        for (int i = tid; i < 16 * g.nflux; i += 256) {
+            const int d = i >> 4, w = i & 15;
+            double m = 0.0;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) m += s_m[(v * g.ndt * 16 + d) * 16 + w];
+            if (wb + w < g.n) Pmb[(size_t)w * g.ldm + d] = m;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 // Host side of the exact form (kernels: jx_exact.hpp; default route): the row as one constant operator on the spline ordinates, planned on
 // the host (plan_exact), uploaded with the work buffers of a chunk (exact_setup), and run per chunk as
 //   jx_walker2_kernel -> jx_ordrow_kernel -> [taps] -> jx_rowsum_tail_kernel   (run_exact).
+// jx_config.dtype 3 ('f32x'): the same plan with the three operators rounded once to fp32, a range guard on the profile derived from them, and
+// jx_ordrow32_kernel in the place of jx_ordrow_kernel; the per-walker kernel, the taps and the tails are the f64 ones.
 #pragma once
 #include "jx_ctx.hpp"
 
@@ -9,6 +11,10 @@ struct ExactBuild {
     int Nk = 0, Nkp = 0, nxt = 0, ng = 0, ng_use = 0, npair = 0, nSj = 0, nfold = 0;
     bool lean = true;
     std::vector<double> Wfk, Typ, Opk;
+    // fp32 products (jx_config.dtype 3): the same three tables rounded once to fp32, and the range guard T = 2^t_log2 on the profile
+    bool f32x = false;
+    std::vector<float> Wfk32, Typ32, Opk32;
+    int t_log2 = 0;
 };
 
 // every pixel, every radius, nothing truncated: nothing here can fail once plan_shared has passed
@@ -36,6 +42,16 @@ static void plan_exact(jx_ctx* ctx, const PlanShared& sh, const std::vector<doub
             jxt::exact_fold_layout(Wy, nrow, r, c.kpc_cm * c.sigma_T / c.m_e, nS, xb.nSj, xb.nxt, xb.ng, xb.Wfk);
         }
     }
+    if (ctx->f32x) {
+        // the tables as built above, in long double then double, rounded once more in the same operand orders; the guard from their absolute row sums
+        xb.f32x = true;
+        jxt::round_to_f32(xb.Typ, xb.Typ32);
+        jxt::round_to_f32(xb.Opk, xb.Opk32);
+        jxt::round_to_f32(xb.Wfk, xb.Wfk32);
+        const int nS = xb.Nkp / 16;
+        xb.t_log2 = jxt::f32_range_guard_log2(jxt::ordinate_layout_abs_rowsum(xb.Typ32, nS, xb.nSj), jxt::row_layout_abs_rowsum(xb.Opk32, nS, xb.nxt, xb.ng),
+                                              xb.nfold ? jxt::row_layout_abs_rowsum(xb.Wfk32, xb.nfold, xb.nxt, xb.ng) : 0.0);
+    }
     xb.ok = true;
 }
 
@@ -55,10 +71,21 @@ static int exact_setup(jx_ctx* ctx, const ExactBuild& xb, long long tW) {
     m.tW = tW;
     m.Nk = xb.Nk; m.Nkp = xb.Nkp; m.nxt = xb.nxt; m.ng = xb.ng; m.ng_use = xb.ng_use;
     m.npair = xb.npair; m.nSj = xb.nSj; m.ldpp = 16 * xb.nSj; m.nfold = xb.nfold; m.lean = xb.lean;
-    if (xb.nfold && (rc = dev_put_l(ctx, m.allocs, xb.Wfk.data(), xb.Wfk.size(), &m.Wfk))) return rc;
     m.cf = nullptr; m.ppi = nullptr;
-    if ((rc = dev_put_l(ctx, m.allocs, xb.Typ.data(), xb.Typ.size(), &m.Typ))) return rc;
-    if ((rc = dev_put_l(ctx, m.allocs, xb.Opk.data(), xb.Opk.size(), &m.Opk))) return rc;
+    m.f32x = xb.f32x; m.t_log2 = xb.t_log2;
+    if (m.f32x) {                                                // (only the fp32 copies are uploaded)
+        if (m.t_log2 < 32) {
+            ctx->err = "dtype 3 (f32x): the fp32 operators of this problem leave the pressure profile a range of 2^" + std::to_string(m.t_log2) + " before an fp32 partial sum could overflow (2^32 required); use dtype 0";
+            return JX_ERR_UNSUPPORTED;
+        }
+        if (xb.nfold && (rc = dev_put_l(ctx, m.allocs, xb.Wfk32.data(), xb.Wfk32.size(), &m.Wfk32))) return rc;
+        if ((rc = dev_put_l(ctx, m.allocs, xb.Typ32.data(), xb.Typ32.size(), &m.Typ32))) return rc;
+        if ((rc = dev_put_l(ctx, m.allocs, xb.Opk32.data(), xb.Opk32.size(), &m.Opk32))) return rc;
+    } else {
+        if (xb.nfold && (rc = dev_put_l(ctx, m.allocs, xb.Wfk.data(), xb.Wfk.size(), &m.Wfk))) return rc;
+        if ((rc = dev_put_l(ctx, m.allocs, xb.Typ.data(), xb.Typ.size(), &m.Typ))) return rc;
+        if ((rc = dev_put_l(ctx, m.allocs, xb.Opk.data(), xb.Opk.size(), &m.Opk))) return rc;
+    }
     if ((rc = dev_new_l(ctx, m.allocs, (size_t)tW * m.Nkp, &m.y, true))) return rc;
     if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.npair * m.ng * 256 * m.nxt, &m.P, true))) return rc;
     // contracted form of the pair-wise kernels: as many data-radii tiles as the epilogue is instantiated for, and fewer data radii than
@@ -71,7 +98,7 @@ static int exact_setup(jx_ctx* ctx, const ExactBuild& xb, long long tW) {
         if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.npair * 16 * m.ldm, &m.Pm, true))) return rc;
         std::vector<double> hE((size_t)nflux * nrow), eop;
         HIPCHK(ctx, hipMemcpy(hE.data(), ctx->d.emat, sizeof(double) * hE.size(), hipMemcpyDeviceToHost));
-        jxt::contract_operand_layout(hE.data(), nflux, nrow, nuse, m.nxt, m.ng_use, eop);
+        jxt::contract_operand_layout(hE.data(), nflux, nrow, nuse, m.nxt, m.ng_use, eop, m.f32x ? 1 : 0);
         if ((rc = dev_put_l(ctx, m.allocs, eop.data(), eop.size(), &m.Eop))) return rc;
     }
     JxRowOp& ro = m.ro;
@@ -198,8 +225,12 @@ static int run_exact(jx_ctx* ctx, Chunk& c) {
         const size_t sh1 = sizeof(double) * (contract ? (size_t)JX_ORD_CT_LDS_DOUBLES(ro.ndt) : (size_t)JX_ORD_LDS_DOUBLES);
         if (tm2 && es.p1stage == 2) HIPCHK(ctx, hipEventRecord(es.e[2], st));
         bool done = false;
+        JxRowOp32 r32{};
+        if (m.f32x) r32 = JxRowOp32{m.Wfk32, m.Opk32, m.Typ32, std::ldexp(1.0, m.t_log2), ctx->d_base};
 #define JX_ORD_GO(Xv) if (!done && m.nxt == Xv) { \
-            if (contract) hipLaunchKernelGGL((jx_ordrow_kernel<Xv, true>), grid, dim3(256), sh1, st, r1); \
+            if (m.f32x && contract) hipLaunchKernelGGL((jx_ordrow32_kernel<Xv, true>), grid, dim3(256), sh1, st, r1, r32); \
+            else if (m.f32x) hipLaunchKernelGGL((jx_ordrow32_kernel<Xv>), grid, dim3(256), sh1, st, r1, r32); \
+            else if (contract) hipLaunchKernelGGL((jx_ordrow_kernel<Xv, true>), grid, dim3(256), sh1, st, r1); \
             else hipLaunchKernelGGL((jx_ordrow_kernel<Xv>), grid, dim3(256), sh1, st, r1); \
             done = true; }
         JX_MIX_NXTS(JX_ORD_GO)

@@ -15,6 +15,7 @@
 //  * tf_hy_table, lowrank_factor(_qr), beam_separable_terms, mix_* : operators of the contracted route (jx_mix.hpp).
 #pragma once
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -1075,16 +1076,64 @@ inline void abel_ordinate_layout(const std::vector<double>& r, double y_scale, i
 // of the second product takes A[m = li][k = lk] = E[16 dt + li][X],
 //     Eop[((((g NXT + t) ndt + dt) 64 + 16 lk + li) 4 + r] = E[16 dt + li][16 (g NXT + t) + lk + 4 r],   ndt = ceil(nflux / 16)
 // (exact zeros for data radii >= nflux and outputs >= nuse): one 32-byte load per lane, tile and dt.
-inline void contract_operand_layout(const double* E, int nflux, int ld, int nuse, int NXT, int ng, std::vector<double>& Eop) {
+// map 1: against the fp32 row product (jx_ordrow32_kernel), whose C / D map leaves lane (lk, li) holding the outputs X = 16 (g NXT + t) + 4 lk + r:
+//     Eop[((((g NXT + t) ndt + dt) 64 + 16 lk + li) 4 + r] = E[16 dt + li][16 (g NXT + t) + 4 lk + r]
+inline void contract_operand_layout(const double* E, int nflux, int ld, int nuse, int NXT, int ng, std::vector<double>& Eop, int map = 0) {
     const int ndt = (nflux + 15) / 16;
     Eop.assign((size_t)ng * NXT * ndt * 256, 0.0);
     for (int gt = 0; gt < ng * NXT; ++gt)
         for (int dt = 0; dt < ndt; ++dt)
             for (int lane = 0; lane < 64; ++lane)
                 for (int r = 0; r < 4; ++r) {
-                    const int d = 16 * dt + (lane & 15), X = 16 * gt + (lane >> 4) + 4 * r;
+                    const int d = 16 * dt + (lane & 15), X = 16 * gt + (map ? 4 * (lane >> 4) + r : (lane >> 4) + 4 * r);
                     if (d < nflux && X < nuse) Eop[(((size_t)gt * ndt + dt) * 64 + lane) * 4 + r] = E[(size_t)d * ld + X];
                 }
+}
+
+// The exact form's operators for the fp32 products (jx_config.dtype 3): a table rounded once to fp32, entry by entry in the same operand
+// order; a nonzero entry below FLT_MIN in magnitude is stored as 0 (whatever the matrix instruction does with subnormal operands).
+inline void round_to_f32(const std::vector<double>& in, std::vector<float>& out) {
+    out.resize(in.size());
+    for (size_t i = 0; i < in.size(); ++i) { const float f = (float)in[i]; out[i] = (std::fabs(f) < FLT_MIN) ? 0.0f : f; }
+}
+
+// Largest absolute row sum of an operator stored in exact_row_layout order ([g][s][4][64][NXT], row x = 16 (g NXT + t) + li): max_x sum_i |Op[x][i]|
+inline double row_layout_abs_rowsum(const std::vector<float>& Opk, int nS, int NXT, int ng) {
+    std::vector<double> rs((size_t)16 * NXT * ng, 0.0);
+    for (int g = 0; g < ng; ++g)
+        for (int s = 0; s < nS; ++s)
+            for (int e = 0; e < 4; ++e)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int t = 0; t < NXT; ++t)
+                        rs[(size_t)16 * (g * NXT + t) + (lane & 15)] += std::fabs((double)Opk[((((size_t)g * nS + s) * 4 + e) * 64 + lane) * NXT + t]);
+    double m = 0.0;
+    for (double v : rs) m = std::max(m, v);
+    return m;
+}
+
+// ... and of the ordinate operator in abel_ordinate_layout order ([s][t][64][4], row k = 16 t + li): max_k sum_j |Ty[k][j]|
+inline double ordinate_layout_abs_rowsum(const std::vector<float>& Typ, int nS, int nSj) {
+    std::vector<double> rs((size_t)16 * nS, 0.0);
+    for (int s = 0; s < nSj; ++s)
+        for (int t = 0; t < nS; ++t)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e) rs[(size_t)16 * t + (lane & 15)] += std::fabs((double)Typ[(((size_t)s * nS + t) * 64 + lane) * 4 + e]);
+    double m = 0.0;
+    for (double v : rs) m = std::max(m, v);
+    return m;
+}
+
+// Range guard of the fp32 products: the largest power of two T (as its exponent) such that no fp32 partial sum can overflow for any profile
+// with max |pp| <= T.  With R_T, R_O, R_F the largest absolute row sums of the fp32 Typ, Opk, Wfk: every partial sum of an ordinate is at
+// most T R_T (1 + u)^n in magnitude, every ordinate too, so every partial sum of a row-product chain -- the upper tile's continues into the
+// fold steps -- is at most T (R_T R_O + R_F) (1 + u)^n; (1 + u)^n < 2 for the n < 2^23 terms of any chain.  With M = max(1, R_T, R_T R_O + R_F)
+// (1: the rounded profile itself) T = 2^floor(log2(FLT_MAX / 2^21 / M)) keeps a margin of 2^20 under FLT_MAX.
+inline int f32_range_guard_log2(double R_T, double R_O, double R_F) {
+    const double M = std::max(1.0, std::max(R_T, R_T * R_O + R_F));
+    if (!std::isfinite(M)) return -1;
+    int ex = 0;
+    (void)std::frexp((double)FLT_MAX / 2097152.0 / M, &ex);      // v = f 2^ex, 0.5 <= f < 1: floor(log2 v) = ex - 1
+    return ex - 1;
 }
 
 // smallest even 2^a 3^b 5^c >= n

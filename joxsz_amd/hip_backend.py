@@ -136,7 +136,9 @@ CONV_MODES = {'auto': 0, 'rocfft': 1, 'custom': 2, 'mix': 2}        # 'custom' =
 ROUTES = {'map': 0, 'operator': 1}
 
 
-DTYPES = {'f64': 0, 'f32': 1, 'f32c': 2}        # 'f32': fp32 spline arrays, fp64 sums; 'f32c': fp32 arithmetic in stages 1 and 2 as well
+# 'f32': fp32 spline arrays, fp64 sums; 'f32c': fp32 arithmetic in stages 1 and 2 as well (both on the contracted forms); 'f32x': the exact
+# form with its two big products on the fp32 matrix cores
+DTYPES = {'f64': 0, 'f32': 1, 'f32c': 2, 'f32x': 3}
 
 
 def config_from_problem(pb, device=0, max_batch=0, fft_pad=0, map_split=0, conv='auto', dtype='f64'):
@@ -260,11 +262,13 @@ class HipContext:
 
     def exact_info(self):
         """Exact form: what the row product hands to the tail (jx_get_exact_info) -- the contracted partials or partial rows, and which of the
-        two the last launch of this context used."""
+        two the last launch of this context used; the arithmetic of the two big products ('f64', or 'f32 products' for dtype='f32x') and, for the
+        latter, log2 of the range guard T: a walker whose pressure profile exceeds T is rejected with -inf."""
         o = (ctypes.c_int32 * 8)()
         self._chk(self.lib.jx_get_exact_info(self._h, o), 'jx_get_exact_info')
         return dict(contracted=bool(o[0]), doubles_per_contracted_partial=int(o[1]), doubles_per_partial_row=int(o[2]),
-                    last_launch={1: 'contracted', 0: 'partial rows'}.get(int(o[3])), data_radii_matrix_in_lds=bool(o[4]), lds_bytes=int(o[5]))
+                    last_launch={1: 'contracted', 0: 'partial rows'}.get(int(o[3])), data_radii_matrix_in_lds=bool(o[4]), lds_bytes=int(o[5]),
+                    arithmetic='f32 products' if o[6] else 'f64', pp_limit_log2=int(o[7]))
 
     def _truncation(self):
         tr = (ctypes.c_double * 12)()
@@ -300,13 +304,13 @@ class HipContext:
                 msgs.append('the truncation guard took the 16-term cap away on this beam / transfer function: %d terms kept '
                             '(SZ stages about %.2fx)' % (d['rank'], rel))
             near = max(d['est_rel_row_err'] / d['bound'], d['est_rel_sz_like_err_box'] / d['bound_sz_like'])
-            if self.dtype != 'f64' and near > 1.0:
+            if self.dtype in ('f32', 'f32c') and near > 1.0:
                 # (an fp32 context is measured but never rebuilt -- its rounding is of the bounds' size -- so nothing takes its 16-term cap or
                 #  its sub-grids away: say what was measured)
                 msgs.append('fp32 context: the contracted tables read %.1e on the row and %.1e on the SZ log-likelihood over the prior box (bounds %.0e / %.0e) and are '
                             'NOT rebuilt for fp32 contexts; build the f64 context (the exact form) or check the walkers with audit()'
                             % (d['est_rel_row_err'], d['est_rel_sz_like_err_box'], d['bound'], d['bound_sz_like']))
-            if not msgs and near > 0.5 and self.dtype == 'f64':
+            if not msgs and near > 0.5 and self.dtype not in ('f32', 'f32c'):
                 msgs.append('the truncation of the low-rank form sits at %.0f %% of its bound (SZ log-likelihood over the prior box %.1e of %.0e): '
                             'slightly different inputs rebuild the tables with more terms (about -35 %% throughput at 31 terms)'
                             % (100 * near, d['est_rel_sz_like_err_box'], d['bound_sz_like']))

@@ -8,6 +8,9 @@ reference's callable (joxsz_funcs.py:593, 600, 622) closely enough to run BASELI
 The log-probability function is any batched callable ``theta[W, ndim] -> logp[W]``:
 ``JoxszPosterior.log_prob`` on a GPU, ``ShardedLogProb`` across GPUs, the oracle on a CPU.
 """
+import math
+from fractions import Fraction
+
 import numpy as np
 
 
@@ -89,6 +92,22 @@ def philox4x32(c0, c1, c2, c3, seed):
     return c0, c1, c2, c3
 
 
+def _fma_scalar(a, b, c):
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        return a * b + c
+    return float(Fraction(a) * Fraction(b) + Fraction(c))                # exact, then ONE rounding to nearest (Fraction -> float rounds correctly)
+
+
+_fma = np.frompyfunc(_fma_scalar, 3, 1)
+
+
+def fma(a, b, c):
+    """a * b + c with one rounding, element by element: what the device's v_fma_f64 computes.  The compiler contracts the proposal's
+    ``t = (a - 1) u + 1`` and ``q = xp - (xp - xi) z`` of the device kernels into one fused multiply-add each, so the host replay fuses the
+    same two (exact rational arithmetic: proposals are few; not a hot path)."""
+    return _fma(np.asarray(a, np.float64), np.asarray(b, np.float64), np.asarray(c, np.float64)).astype(np.float64)
+
+
 def _u01(hi, lo):
     return ((((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64)) * (1.0 / 9007199254740992.0)
 
@@ -119,11 +138,11 @@ class DeviceStretchMove:
                 s1, s2 = hs * half, (1 - hs) * half
                 r = philox4x32(i, 2 * it + hs, 0, 0, self.seed)
                 u1, u2 = _u01(r[0], r[1]), _u01(r[2], r[3])
-                t = (self.a - 1.0) * u1 + 1.0
+                t = fma(self.a - 1.0, u1, 1.0)                    # (fused on the device: see fma)
                 z = (t * t) / self.a
                 j = np.minimum((u2 * half).astype(np.int64), half - 1)
                 xp, xi = x[s2 + j], x[s1:s1 + half]
-                q = xp - (xp - xi) * z[:, None]
+                q = fma(-(xp - xi), z[:, None], xp)
                 lq = np.asarray(log_prob(q), dtype=np.float64)
                 u3 = _u01(*philox4x32(i, 2 * it + hs, 1, 0, self.seed)[:2])
                 with np.errstate(invalid='ignore'):
