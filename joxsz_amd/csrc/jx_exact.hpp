@@ -216,6 +216,20 @@ __device__ __forceinline__ void jx_row_epilogue(const JxDev& c, const JxRowOp& g
 #define JX_CT_NDT 2                    // data-radii tiles of 16 the contracted epilogue is instantiated for (nflux <= 32; beyond: partial rows)
 #define JX_ORD_CT_LDS_DOUBLES(ndt) ((4 * (ndt) * 256 + 16 * 36) > JX_ORD_LDS_DOUBLES ? (4 * (ndt) * 256 + 16 * 36) : JX_ORD_LDS_DOUBLES)
 
+// The waves' partial ordinates of the pair's two tiles added in wave order into s_yt[16 walkers][36] (and stored for calls with taps), shared
+// by both kernels (called by every thread between two barriers).  WM: a wave's [16][16] per tile is [walker][ordinate] (the f64 D map) or
+// [ordinate][walker] (the fp32 one)
+template <bool WM>
+__device__ __forceinline__ void jx_ord_add_parts(const double* s1, double* s_yt, double* y, int tid, int p, int q, int nS, int wb, int n, int ldy) {
+    for (int idx = tid; idx < 512; idx += 256) {
+        const int t = idx >> 8, hi = (idx >> 4) & 15, lo = idx & 15, w = WM ? hi : lo, cc = WM ? lo : hi;
+        const double v = ((s1[((0 * 2 + t) * 16 + hi) * 16 + lo] + s1[((1 * 2 + t) * 16 + hi) * 16 + lo]) + s1[((2 * 2 + t) * 16 + hi) * 16 + lo]) + s1[((3 * 2 + t) * 16 + hi) * 16 + lo];
+        s_yt[w * 36 + 16 * t + cc] = v;
+        const int tile = t ? q : p;
+        if (y && tile < nS && wb + w < n) y[(size_t)(wb + w) * ldy + 16 * tile + cc] = v;
+    }
+}
+
 template <int NXT, bool CT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 jx_ordrow_kernel(JxRowOp g) {
@@ -325,13 +339,7 @@ jx_ordrow_kernel(JxRowOp g) {
         }
     }
     __syncthreads();
-    for (int idx = tid; idx < 512; idx += 256) {
-        const int t = idx >> 8, w = (idx >> 4) & 15, cc = idx & 15;
-        const double v = ((s1[((0 * 2 + t) * 16 + w) * 16 + cc] + s1[((1 * 2 + t) * 16 + w) * 16 + cc]) + s1[((2 * 2 + t) * 16 + w) * 16 + cc]) + s1[((3 * 2 + t) * 16 + w) * 16 + cc];
-        s_yt[w * 36 + 16 * t + cc] = v;
-        const int tile = t ? q : p;
-        if (g.y && tile < g.nS && wb + w < g.n) g.y[(size_t)(wb + w) * g.ldy + 16 * tile + cc] = v;
-    }
+    jx_ord_add_parts<true>(s1, s_yt, g.y, tid, p, q, g.nS, wb, g.n, g.ldy);
     __syncthreads();
     JX_STAMP(g, 3);
 
@@ -547,13 +555,7 @@ jx_ordrow32_kernel(JxRowOp g, JxRowOp32 h) {
         *reinterpret_cast<jx_ro_v4d*>(s1 + ((wv * 2 + 1) * 16 + li) * 16 + 4 * lk) = yq;
     }
     __syncthreads();
-    for (int idx = tid; idx < 512; idx += 256) {
-        const int t = idx >> 8, cc = (idx >> 4) & 15, w = idx & 15;
-        const double v = ((s1[((0 * 2 + t) * 16 + cc) * 16 + w] + s1[((1 * 2 + t) * 16 + cc) * 16 + w]) + s1[((2 * 2 + t) * 16 + cc) * 16 + w]) + s1[((3 * 2 + t) * 16 + cc) * 16 + w];
-        s_yt[w * 36 + 16 * t + cc] = v;
-        const int tile = t ? q : p;
-        if (g.y && tile < g.nS && wb + w < g.n) g.y[(size_t)(wb + w) * g.ldy + 16 * tile + cc] = v;
-    }
+    jx_ord_add_parts<false>(s1, s_yt, g.y, tid, p, q, g.nS, wb, g.n, g.ldy);
     __syncthreads();
 
     // ---- this pair's share of the row product; wave v owns the output tiles v, v + 4
@@ -561,7 +563,7 @@ jx_ordrow32_kernel(JxRowOp g, JxRowOp32 h) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { yp[e] = (float)s_yt[li * 36 + 4 * lk + e]; yq[e] = (float)s_yt[li * 36 + 16 + 4 * lk + e]; }
     constexpr int NTT = (NXT + 3) / 4;
-    int lane_g = lane;                                          // (as in jx_ordrow_kernel: made opaque per group in the contracted form)
+    int lane_g = lane;                                          // (made opaque per group in the contracted form: the steer described in jx_ordrow_kernel)
     double* s_m = sm_or32;                                      // contracted form: [4][ndt][16][16] wave sums (the reduction area is dead behind the barrier above)
     for (int gi = 0; gi < g.ng; ++gi) {
 #ifdef __HIP_DEVICE_COMPILE__

@@ -2,7 +2,8 @@
 // the host (plan_exact), uploaded with the work buffers of a chunk (exact_setup), and run per chunk as
 //   jx_walker2_kernel -> jx_ordrow_kernel -> [taps] -> jx_rowsum_tail_kernel   (run_exact).
 // jx_config.dtype 3 ('f32x'): the same plan with the three operators rounded once to fp32, a range guard on the profile derived from them, and
-// jx_ordrow32_kernel in the place of jx_ordrow_kernel; the per-walker kernel, the taps and the tails are the f64 ones.
+// jx_ordrow32_kernel in the place of jx_ordrow_kernel (same grid, LDS and JxRowOp; its tables, the guard and the priors come
+// in JxRowOp32); the per-walker kernel, the taps and the tails are the f64 ones.
 #pragma once
 #include "jx_ctx.hpp"
 
