@@ -68,12 +68,19 @@ struct JxRowOp {
     const double* cfac;            // [n][nrow] conversion factors (per-walker kernel), written up to the outputs of this launch's groups
     const double* Eop;             // [ng][NXT][ndt][64][4] data-radii matrix as the A operand of the epilogue's product (jxt::contract_operand_layout)
     double* Pm;                    // [walker tiles][npair][16][ldm] contracted partials
-    long long* stamps;             // diagnostic build only: [blocks][8] wall-clock stamps (100 MHz) of jx_ordrow_kernel's phases
+    long long* stamps;             // diagnostic build only: [blocks][JX_STAMP_LD] wall-clock stamps (100 MHz) of jx_ordrow_kernel's phases
 };
 #ifdef JOXSZ_ABLATIONS
-#define JX_STAMP(g, k) do { if ((g).stamps && threadIdx.x == 0) (g).stamps[(size_t)blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
+#define JX_STAMP_LD 16
+#define JX_STAMP(g, k) do { if ((g).stamps && threadIdx.x == 0) (g).stamps[(size_t)blockIdx.x * JX_STAMP_LD + (k)] = wall_clock64(); } while (0)
+// per wave: the end of its epilogue in front of the block's last barrier, slots 8-11, and where it ran, slots 12-15 (the hardware id
+// register -- SIMD, compute unit, shader engine -- with the XCD number above it)
+#define JX_STAMP_WAVE(g, lane, w) do { if ((g).stamps && (lane) == 0) { \
+        (g).stamps[(size_t)blockIdx.x * JX_STAMP_LD + 8 + (w)] = wall_clock64(); \
+        (g).stamps[(size_t)blockIdx.x * JX_STAMP_LD + 12 + (w)] = (long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((long long)(__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 15) << 32); } } while (0)
 #else
 #define JX_STAMP(g, k) do { } while (0)
+#define JX_STAMP_WAVE(g, lane, w) do { } while (0)
 #endif
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -278,7 +285,8 @@ jx_ordrow_kernel(JxRowOp g) {
     auto load_cf = [&](int gi) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
-            const int X0 = gi * 16 * NXT + 16 * min(wv + 4 * tt, NXT - 1) + lk;
+            if (wv + 4 * tt >= NXT) continue;                   // (wave-uniform: no factors for a tile the wave does not own)
+            const int X0 = gi * 16 * NXT + 16 * (wv + 4 * tt) + lk;
 #pragma unroll
             for (int r = 0; r < 4; ++r) cfv[tt][r] = g.cfac[(size_t)wq * g.nrow + min(X0 + 4 * r, g.nrow - 1)];
         }
@@ -300,14 +308,18 @@ jx_ordrow_kernel(JxRowOp g) {
     {
         int s = p + wv;
         jx_ro_v4d a0, bp0, bq0, a1, bp1, bq1;
-        const int tq = hasq ? q : p;                            // (no upper tile: its loads repeat the lower one's, its products are skipped)
-        if (s < g.nSj) { a0 = load_a(s); bp0 = load_b(s, p); bq0 = load_b(s, tq); }
+        // the upper tile's operator is requested only for the steps that multiply it (the Abel matrix is triangular: s >= q; wave-uniform)
+        auto load_bq = [&](int s, jx_ro_v4d& b) { if (hasq && s >= q) b = load_b(s, q); };
+#ifdef JOXSZ_ABLATIONS
+        bq0 = bq1 = jx_ro_v4d{0.0, 0.0, 0.0, 0.0};              // (the diagnostic forms below read them whatever the step)
+#endif
+        if (s < g.nSj) { a0 = load_a(s); bp0 = load_b(s, p); load_bq(s, bq0); }
 #ifdef JOXSZ_ABLATIONS
         if (g.stamps) { if (a0[0] + bp0[0] + bq0[0] == 1.234e300) ap[0][0] = 1.0; JX_STAMP(g, 1); }
 #endif
         for (; s < g.nSj; s += 8) {
             const int s1n = s + 4, s2n = s + 8;
-            if (s1n < g.nSj) { a1 = load_a(s1n); bp1 = load_b(s1n, p); bq1 = load_b(s1n, tq); }
+            if (s1n < g.nSj) { a1 = load_a(s1n); bp1 = load_b(s1n, p); load_bq(s1n, bq1); }
             if (!JX_DBG(g, 1)) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) ap[e & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[e], bp0[e], ap[e & 1], 0, 0, 0);
@@ -317,7 +329,7 @@ jx_ordrow_kernel(JxRowOp g) {
                 for (int e = 0; e < 4; ++e) aq[e & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[e], bq0[e], aq[e & 1], 0, 0, 0);
             }
             if (s1n < g.nSj) {
-                if (s2n < g.nSj) { a0 = load_a(s2n); bp0 = load_b(s2n, p); bq0 = load_b(s2n, tq); }
+                if (s2n < g.nSj) { a0 = load_a(s2n); bp0 = load_b(s2n, p); load_bq(s2n, bq0); }
                 if (!JX_DBG(g, 1)) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) ap[e & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[e], bp1[e], ap[e & 1], 0, 0, 0);
@@ -437,6 +449,7 @@ jx_ordrow_kernel(JxRowOp g) {
                 }
         }
     }
+    JX_STAMP_WAVE(g, lane, tid >> 6);
     if (CT) {
         // ---- the block's share of the model at the data radii: the waves' [ndt][16 d][16 w] sums are added in wave order (the pair's
         //      ordinates behind them in LDS stay untouched: no barrier in front of the row product)

@@ -128,26 +128,26 @@ static int exact_setup(jx_ctx* ctx, const ExactBuild& xb, long long tW) {
 // printed once, at the 40th launch
 static int ordrow_stamps(jx_ctx* ctx, hipStream_t st, int n, JxRowOp& ro) {
     static long long* stamps = nullptr;
-    if (!stamps) { HIPCHK(ctx, hipMalloc((void**)&stamps, sizeof(long long) * 8 * 65536)); }
+    if (!stamps) { HIPCHK(ctx, hipMalloc((void**)&stamps, sizeof(long long) * JX_STAMP_LD * 65536)); }
     ro.stamps = stamps;
     static int calls = 0;
     if (++calls != 40) return JX_OK;
     HIPCHK(ctx, hipStreamSynchronize(st));
     const int nb = 8 * ((((n + 15) / 16) + 7) / 8) * ro.npair;
-    std::vector<long long> h((size_t)nb * 8);
+    std::vector<long long> h((size_t)nb * JX_STAMP_LD);
     HIPCHK(ctx, hipMemcpy(h.data(), stamps, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
     long long t0 = h[0];
-    for (int b = 0; b < nb; ++b) t0 = std::min(t0, h[(size_t)b * 8]);
+    for (int b = 0; b < nb; ++b) t0 = std::min(t0, h[(size_t)b * JX_STAMP_LD]);
     double mx[5] = {0, 0, 0, 0, 0}, sm[5] = {0, 0, 0, 0, 0};
     for (int b = 0; b < nb; ++b)
-        for (int k = 0; k < 5; ++k) { const double v = (h[(size_t)b * 8 + k] - t0) * 0.01; mx[k] = std::max(mx[k], v); sm[k] += v / nb; }
+        for (int k = 0; k < 5; ++k) { const double v = (h[(size_t)b * JX_STAMP_LD + k] - t0) * 0.01; mx[k] = std::max(mx[k], v); sm[k] += v / nb; }
     fprintf(stderr, "ordrow stamps (us after the first block's start; mean / max over %d blocks): start %.2f/%.2f  first loads %.2f/%.2f  k loop %.2f/%.2f  ordinates %.2f/%.2f  end %.2f/%.2f\n",
             nb, sm[0], mx[0], sm[1], mx[1], sm[2], mx[2], sm[3], mx[3], sm[4], mx[4]);
     {                                                            // where the late first operands are: by XCD, by eighth of the grid, and the ten latest blocks
         double bx[8] = {0}, bo[8] = {0}; int cx[8] = {0}, co[8] = {0}, late = 0;
         std::vector<std::pair<double, int>> fl;
         for (int b = 0; b < nb; ++b) {
-            const double v = (h[(size_t)b * 8 + 1] - h[(size_t)b * 8]) * 0.01;
+            const double v = (h[(size_t)b * JX_STAMP_LD + 1] - h[(size_t)b * JX_STAMP_LD]) * 0.01;
             bx[b & 7] += v; ++cx[b & 7]; bo[b * 8 / nb] += v; ++co[b * 8 / nb]; if (v > 3.0) ++late;
             fl.push_back({v, b});
         }
@@ -157,16 +157,55 @@ static int ordrow_stamps(jx_ctx* ctx, hipStream_t st, int n, JxRowOp& ro) {
         fprintf(stderr, " | by eighth of the grid:");
         for (int k = 0; k < 8; ++k) fprintf(stderr, " %.2f", bo[k] / std::max(1, co[k]));
         fprintf(stderr, " | %d blocks beyond 3 us; latest:", late);
-        for (int k = 0; k < 10 && k < (int)fl.size(); ++k) fprintf(stderr, " %d(%.1f, start %.1f)", fl[k].second, fl[k].first, (h[(size_t)fl[k].second * 8] - t0) * 0.01);
+        for (int k = 0; k < 10 && k < (int)fl.size(); ++k) fprintf(stderr, " %d(%.1f, start %.1f)", fl[k].second, fl[k].first, (h[(size_t)fl[k].second * JX_STAMP_LD] - t0) * 0.01);
         fprintf(stderr, "\n");
     }
     for (int pp_ = 0; pp_ < ro.npair; ++pp_) {                  // per pair: mean first loads | k loop | end
         double a[3] = {0, 0, 0}, e_max = 0; int cnt = 0;
         for (int b = 0; b < nb; ++b) if ((b >> 3) % ro.npair == pp_) {
-            a[0] += (h[(size_t)b * 8 + 1] - t0) * 0.01; a[1] += (h[(size_t)b * 8 + 2] - t0) * 0.01; a[2] += (h[(size_t)b * 8 + 4] - t0) * 0.01;
-            e_max = std::max(e_max, (h[(size_t)b * 8 + 4] - t0) * 0.01); ++cnt;
+            a[0] += (h[(size_t)b * JX_STAMP_LD + 1] - t0) * 0.01; a[1] += (h[(size_t)b * JX_STAMP_LD + 2] - t0) * 0.01; a[2] += (h[(size_t)b * JX_STAMP_LD + 4] - t0) * 0.01;
+            e_max = std::max(e_max, (h[(size_t)b * JX_STAMP_LD + 4] - t0) * 0.01); ++cnt;
         }
         fprintf(stderr, "  pair %2d: first loads %.2f  k loop %.2f  end %.2f (max %.2f)\n", pp_, a[0] / cnt, a[1] / cnt, a[2] / cnt, e_max);
+    }
+    {   // per wave: the end of the epilogue (in front of the block's last barrier) after the block's ordinates stamp
+        double aw[4] = {0, 0, 0, 0}, mw[4] = {0, 0, 0, 0};
+        for (int b = 0; b < nb; ++b)
+            for (int w = 0; w < 4; ++w) {
+                const double v = (h[(size_t)b * JX_STAMP_LD + 8 + w] - h[(size_t)b * JX_STAMP_LD + 3]) * 0.01;
+                aw[w] += v / nb; mw[w] = std::max(mw[w], v);
+            }
+        fprintf(stderr, "  epilogue end after the block's ordinates, mean (max) by wave: %.2f (%.2f) %.2f (%.2f) %.2f (%.2f) %.2f (%.2f)\n",
+                aw[0], mw[0], aw[1], mw[1], aw[2], mw[2], aw[3], mw[3]);
+        // where the waves ran: hardware id bits 5:4 SIMD, 15:8 compute unit with shader array and engine, XCD number above bit 32
+        std::map<long long, std::vector<int>> cu;                // compute unit -> its blocks
+        std::map<long long, int> simd_tiles;                     // (compute unit, SIMD) -> output tiles owned by the roles that ran there
+        int off[4] = {0, 0, 0, 0}, split = 0;
+        for (int b = 0; b < nb; ++b) {
+            const long long* hb = &h[(size_t)b * JX_STAMP_LD + 12];
+            const long long key0 = (hb[0] >> 32 << 8) | ((hb[0] >> 8) & 255);
+            cu[key0].push_back(b);
+            ++off[(int)((hb[0] >> 4) & 3)];
+            for (int w = 0; w < 4; ++w) {
+                const long long key = (hb[w] >> 32 << 8) | ((hb[w] >> 8) & 255);
+                if (key != key0 || (int)((hb[w] >> 4) & 3) != (int)(((hb[0] >> 4) & 3) + w) % 4) ++split;
+                simd_tiles[key * 4 + ((hb[w] >> 4) & 3)] += (w + 4 < 6) ? 2 : 1;   // (six output tiles, wave w owns w and w + 4: the flagship instance)
+            }
+        }
+        int hist[8] = {0}, tmax_sum = 0; std::map<long long, int> cumax;
+        for (auto& kv : cu) ++hist[std::min<size_t>(7, kv.second.size())];
+        for (auto& kv : simd_tiles) cumax[kv.first >> 2] = std::max(cumax[kv.first >> 2], kv.second);
+        int worst = 0; for (auto& kv : cumax) { tmax_sum += kv.second; worst = std::max(worst, kv.second); }
+        fprintf(stderr, "  placement: %d compute units; blocks per unit 1..7+: %d %d %d %d %d %d %d; SIMD of wave 0: %d %d %d %d; waves off (SIMD of wave 0 + w) or off the unit: %d\n",
+                (int)cu.size(), hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], off[0], off[1], off[2], off[3], split);
+        fprintf(stderr, "  output tiles on the busiest SIMD of a unit (six-tile instance): mean %.2f, worst %d\n", tmax_sum / std::max(1.0, (double)cumax.size()), worst);
+        int shown = 0;
+        for (auto& kv : cu) {
+            if (shown++ >= 12) break;
+            fprintf(stderr, "    unit %llx:", kv.first);
+            for (int b : kv.second) fprintf(stderr, " id %d (jj %d, start %.2f, wave0 SIMD %d)", b, b >> 3, (h[(size_t)b * JX_STAMP_LD] - t0) * 0.01, (int)((h[(size_t)b * JX_STAMP_LD + 12] >> 4) & 3));
+            fprintf(stderr, "\n");
+        }
     }
     return JX_OK;
 }
