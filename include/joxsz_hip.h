@@ -406,7 +406,8 @@ int  jx_get_truncation(jx_ctx* ctx, double out[12]);
  *   5 operator of the matrix-core product, Op[(kappa * 16 + (x & 15)) * ntile + (x >> 4)]: geom = {4 ksteps, 16, ntile, 8}
  * exact form (the others belong to the contracted forms):
  *   6 Compton-y ordinates of the last chunk, walker-major y[w][k]: geom = {1, tW, Nkp, 8} (written by calls with taps, by the reference kernels and with JOXSZ_X_FOLD=0: the timed path keeps them in LDS)
- *   7 row operator as the matrix cores read it, Opk[(((g nS + s) 4 + e) 64 + lane) nxt + t] = Wy[16 (g nxt + t) + (lane & 15)][16 s + 4 (lane >> 4) + e]: geom = {ng nS 4, 64, nxt, 8} */
+ *   7 row operator as the pair-wise kernels read it, tile-major, Opk[(((g nS + s) nxt + t) 64 + lane) 4 + e] = Wy[16 (g nxt + t) + (lane & 15)][16 s + 4 (lane >> 4) + e]: geom = {ng nS nxt, 64, 4, element bytes}
+ *     (4 with dtype 3: the fp32 rounding; not with JOXSZ_X_PAIRWISE=0, whose kernel reads the lane-major table) */
 int  jx_debug_workspace(jx_ctx* ctx, int which, void** dev, int32_t geom[4]);
 /* Duration (ms, HIP events on the context's stream, mean of `repeats` launches) of the Abel + map kernel writing the full
  * S x S Compton-y map of `nwalkers` walkers whose parameter vectors are at theta_dev: the kernel BASELINE's metric is worded

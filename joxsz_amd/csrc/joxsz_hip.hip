@@ -1589,9 +1589,9 @@ int jx_debug_workspace(jx_ctx* ctx, int which, void** dev, int32_t geom[4]) {
     if (ctx->exact.ready) {
         const ExactBack& x = ctx->exact;
         if (which == 6) { *dev = x.y; geom[0] = 1; geom[1] = (int)x.tW; geom[2] = x.Nkp; geom[3] = 8; return JX_OK; }
-        if (which == 7) { *dev = x.f32x ? (void*)x.Opk32 : (void*)x.Opk; geom[0] = x.ng * (x.Nkp / 16) * 4; geom[1] = 64; geom[2] = x.nxt; geom[3] = x.f32x ? 4 : 8; return JX_OK; }
+        if (which == 7 && x.pairwise) { *dev = x.f32x ? (void*)x.Opk32 : (void*)x.Opk; geom[0] = x.ng * (x.Nkp / 16) * x.nxt; geom[1] = 64; geom[2] = 4; geom[3] = x.f32x ? 4 : 8; return JX_OK; }
         if (which == 0 && ctx->d_img) { *dev = ctx->d_img; geom[0] = ctx->chunk; geom[1] = ctx->d.q_nb; geom[2] = (int)ctx->d.img_ld; geom[3] = 8; return JX_OK; }
-        ctx->err = "exact form: work buffers 6 (ordinates [1][tW][Nkp]) and 7 (row operator) -- and 0 after a y_2d tap -- exist; the others belong to the contracted forms";
+        ctx->err = "exact form: work buffers 6 (ordinates [1][tW][Nkp]) and 7 (row operator of the pair-wise kernels, tile-major [ng nS nxt][64][4]; not with JOXSZ_X_PAIRWISE=0) -- and 0 after a y_2d tap -- exist; the others belong to the contracted forms";
         return JX_ERR_UNSUPPORTED;
     }
     if (which >= 6) { ctx->err = "work buffers 6 and 7 belong to the exact form"; return JX_ERR_UNSUPPORTED; }

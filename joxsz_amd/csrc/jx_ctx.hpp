@@ -88,7 +88,8 @@ struct ExactBack {
     bool ready = false;                // the exact form is this context's route
     int Nk = 0, Nkp = 0, nxt = 0, ng = 0, ng_use = 0, npair = 0, nSj = 0, ldpp = 0, nfold = 0;
     bool lean = true;                  // JOXSZ_X_FOLD=0 clears it: the timed path then stores the ordinates and forms every tile, like a call with taps
-    double *Wfk = nullptr;             // odd number of ordinate tiles: the last one's share of the row as an operator on the profile (timed path; jxt::exact_fold_layout)
+    double *Wfk = nullptr;             // odd number of ordinate tiles: the last one's share of the row as an operator on the profile (timed path; jxt::exact_fold_layout, tile-major)
+                                       // Opk: tile-major (jxt::row_tile_major) for the pair-wise kernels; with JOXSZ_X_PAIRWISE=0 in exact_row_layout's own order, for jx_rowop_tail_kernel
     double *Typ = nullptr, *Opk = nullptr, *y = nullptr, *cf = nullptr, *P = nullptr, *ppi = nullptr;
     bool pairwise = true;              // JOXSZ_X_PAIRWISE=0: the ordinates read back by one block per 16 walkers (jx_rowop_tail_kernel)
     bool contract = true;              // JOXSZ_X_CONTRACT=0: the pair-wise kernels exchange partial rows in every call (with it: only in calls with row / brightness taps)

@@ -35,7 +35,7 @@
 // Operand layouts (v_mfma_f64_16x16x4: A lane l = A[l & 15][4 s + (l >> 4)], B lane l = B[4 s + (l >> 4)][l & 15], D register g of
 // lane l = D[(l >> 4) + 4 g][l & 15]).  The order of the K index is free as long as A and B agree on it: a lane takes FOUR
 // consecutive values of its walker in one 32-byte load, v[w][16 s + 4 lk + e], e = 0..3, and feeds element e to sub-step e; the
-// operators are stored to match (jxt::exact_row_layout, jxt::abel_ordinate_layout).
+// operators are stored to match (jxt::exact_row_layout and jxt::row_tile_major, jxt::abel_ordinate_layout).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,8 +54,9 @@ struct JxRowOp {
     int dbg;                       // diagnostic build only (make ABLATIONS=1; JOXSZ_X_DBG): 1 no matrix instructions in the ordinate product, 2 no row product, 4 no partial-row stores, 8 no operator loads
     int ldpp, nSj, npair;          // ordinate product: doubles per profile (16 nSj, zeros behind the grid), macro steps of 16 radii, column-tile pairs
     int nfold, s0f;                // folded form (odd nS, timed path): macro steps of 16 radii of the last ordinate tile's share of the row, the first of them; 0: none
-    const double* Wfk;             // [ng_all][nfold][4][64][NXT]  the last ordinate tile's share of the row as an operator on the profile (jxt::exact_fold_layout)
-    const double* Opk;             // [ng_all][nS][4][64][NXT]     row operator (jxt::exact_row_layout)
+    const double* Wfk;             // [ng_all][nfold][NXT][64][4]  the last ordinate tile's share of the row as an operator on the profile (jxt::exact_fold_layout, tile-major: jxt::row_tile_major)
+    const double* Opk;             // [ng_all][nS][NXT][64][4]     row operator, tile-major (jxt::exact_row_layout, then jxt::row_tile_major); JOXSZ_X_PAIRWISE=0: [ng_all][nS][4][64][NXT],
+                                   //                              exact_row_layout's own order, which jx_rowop_tail_kernel reads (jx_ordrow_kernel then forms no row product)
     const double* Typ;             // [nSj][nS][64][4]             ordinate operator (jxt::abel_ordinate_layout)
     const double* pp;              // [n][ldpp] pressure profiles (jx_prep_kernel)
     double* y;                     // [tW][ldy] ordinates, walker-major; null: not stored (timed path: nothing reads them)
@@ -262,18 +263,18 @@ jx_ordrow_kernel(JxRowOp g) {
 #pragma unroll
     for (int e = 0; e < 2; ++e) { ap[e] = jx_ro_v4d{0.0, 0.0, 0.0, 0.0}; aq[e] = jx_ro_v4d{0.0, 0.0, 0.0, 0.0}; }
     constexpr int NTT = (NXT + 3) / 4;
-    double bpv[NTT][4], bqv[NTT][4];
-    int lane_g = lane;                                          // (the lane again, for the addresses of the row product's groups: see there)
+    jx_ro_v4d bpv[NTT], bqv[NTT];
+    unsigned lane_g = 32u * lane;                               // (the lane's byte offset into a [64 lanes][4] operand block, for the addresses of the row product's groups: see there)
+    // one 32-byte load of the lane's four values of an operand block: a wave-uniform address plus the lane's 32-bit byte offset
+    auto load_blk = [&](const double* blk) -> jx_ro_v4d { return *reinterpret_cast<const jx_ro_v4d*>(reinterpret_cast<const char*>(blk) + lane_g); };
+    // the row operator tile-major (jxt::row_tile_major): one 32-byte load per lane, ordinate tile and output tile, a wave's load one 2 KB run
     auto load_op = [&](int gi) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
             const int t = min(wv + 4 * tt, NXT - 1);
-            const double* __restrict__ ob = g.Opk + ((size_t)gi * g.nS * 256 + lane_g) * NXT + t;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bpv[tt][e] = ob[((size_t)p * 4 + e) * 64 * NXT];
-                bqv[tt][e] = ob[((size_t)(hasq ? q : p) * 4 + e) * 64 * NXT];
-            }
+            const double* __restrict__ ob = g.Opk + ((size_t)gi * g.nS * NXT + t) * 256;
+            bpv[tt] = load_blk(ob + (size_t)p * NXT * 256);
+            bqv[tt] = load_blk(ob + (size_t)(hasq ? q : p) * NXT * 256);
         }
     };
 
@@ -281,11 +282,14 @@ jx_ordrow_kernel(JxRowOp g) {
     // 16 t + lk + 4 r).  The k loop and the row product leave no 16 registers for them at four waves per SIMD (requested ahead of the k loop
     // the build spills them), so they are requested with the data-radii matrix, behind the row product.  (One value per lane of their
     // lines requested ahead of the k loop, to have them in this XCD's L2 by then: measured, 0.15 us slower per step, not kept.)
-    double cfv[NTT][4];
-    auto load_cf = [&](int gi) {
+    auto load_cf = [&](int gi, double (&cfv)[NTT][4]) {
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
-            if (wv + 4 * tt >= NXT) continue;                   // (wave-uniform: no factors for a tile the wave does not own)
+            if (wv + 4 * tt >= NXT) {                           // (wave-uniform: no factors for a tile the wave does not own; defined all the same,
+#pragma unroll
+                for (int r = 0; r < 4; ++r) cfv[tt][r] = 0.0;   //  or the registers stay reserved around the whole loop over the groups)
+                continue;
+            }
             const int X0 = gi * 16 * NXT + 16 * (wv + 4 * tt) + lk;
 #pragma unroll
             for (int r = 0; r < 4; ++r) cfv[tt][r] = g.cfac[(size_t)wq * g.nrow + min(X0 + 4 * r, g.nrow - 1)];
@@ -299,7 +303,7 @@ jx_ordrow_kernel(JxRowOp g) {
             const int t = min(wv + 4 * tt, NXT - 1);
 #pragma unroll
             for (int dt = 0; dt < JX_CT_NDT; ++dt)
-                ev[tt][dt] = *reinterpret_cast<const jx_ro_v4d*>(g.Eop + ((((size_t)gi * NXT + t) * g.ndt + min(dt, g.ndt - 1)) * 64 + lane_g) * 4);
+                ev[tt][dt] = load_blk(g.Eop + (((size_t)gi * NXT + t) * g.ndt + min(dt, g.ndt - 1)) * 256);
         }
     };
 
@@ -361,10 +365,12 @@ jx_ordrow_kernel(JxRowOp g) {
     double* s_m = sm_or;                                        // contracted form: [4][ndt][16][16] wave sums (the reduction area is dead behind the barrier above)
     for (int gi = 0; gi < (JX_DBG(g, 2) ? 0 : g.ng); ++gi) {
 #ifdef __HIP_DEVICE_COMPILE__
-        // (contracted form: the lane number is made opaque per group, so that the lane parts of the operand addresses are formed where they
+        // (contracted form: the lane's offset is made opaque per group, so that the lane parts of the operand addresses are formed where they
         //  are used and die there, instead of being kept in registers from in front of the loop: the epilogue's operands need them.  This
         //  steers the register allocator and nothing else: after a compiler change re-check with
-        //  make EXTRA=-Rpass-analysis=kernel-resource-usage that <6, true> has 0 bytes of scratch at four waves per SIMD)
+        //  make EXTRA=-Rpass-analysis=kernel-resource-usage that <6, true> has 0 bytes of scratch at four waves per SIMD; DESIGN 6.2.
+        //  Re-checked with the tile-major operators: without it <5, true> and <6, true> get 52 bytes of scratch.  The same figures need the
+        //  zeros that define the factors and the share of a tile the wave does not own, load_cf and the row product below.)
         if (CT) asm volatile("" : "+v"(lane_g));
 #endif
         load_op(gi);
@@ -373,15 +379,13 @@ jx_ordrow_kernel(JxRowOp g) {
         // profile (requested with the row operator above: one trip; requesting both ahead of the reduction was measured twice: slower)
         const bool fold = p < g.nfold;
         jx_ro_v4d af = jx_ro_v4d{0.0, 0.0, 0.0, 0.0};
-        double bfv[NTT][4];
+        jx_ro_v4d bfv[NTT];
         if (fold) {
             af = load_a(g.s0f + p);
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
                 const int t = min(wv + 4 * tt, NXT - 1);
-                const double* __restrict__ ob = g.Wfk + ((((size_t)gi * g.nfold + p) * 4) * 64 + lane_g) * NXT + t;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bfv[tt][e] = ob[(size_t)e * 64 * NXT];
+                bfv[tt] = load_blk(g.Wfk + (((size_t)gi * g.nfold + p) * NXT + t) * 256);
             }
         }
         double* __restrict__ Pb = g.P + (((size_t)wt * g.npair + p) * g.ng + gi) * (size_t)(256 * NXT);
@@ -401,9 +405,9 @@ jx_ordrow_kernel(JxRowOp g) {
                     for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(bfv[tt][e], af[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(af[e], bfv[tt][e], c1, 0, 0, 0);
                     for (int sf = p + g.npair; sf < g.nfold; sf += g.npair) {        // (more macro steps than pairs: short grids only)
                         const jx_ro_v4d a2 = load_a(g.s0f + sf);
-                        const double* __restrict__ ob = g.Wfk + ((((size_t)gi * g.nfold + sf) * 4) * 64 + lane_g) * NXT + t;
+                        const jx_ro_v4d b2 = load_blk(g.Wfk + (((size_t)gi * g.nfold + sf) * NXT + t) * 256);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(ob[(size_t)e * 64 * NXT], a2[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(a2[e], ob[(size_t)e * 64 * NXT], c1, 0, 0, 0);
+                        for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f64_16x16x4f64(b2[e], a2[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f64_16x16x4f64(a2[e], b2[e], c1, 0, 0, 0);
                     }
                 }
                 const jx_ro_v4d cs = c0 + c1;
@@ -414,13 +418,17 @@ jx_ordrow_kernel(JxRowOp g) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) if (!JX_DBG(g, 4) || cs[r] == 1.234e300) Pb[(size_t)(lk + 4 * r) * (16 * NXT) + 16 * t + li] = cs[r];
                 }
+            } else if (CT) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) bv[tt][r] = 0.0;     // (never read: defined, like the factors of a tile the wave does not own)
             }
         }
         if (CT) {
             // ---- the group's share of the model at the data radii, m^T[d = 16 dt + lk + 4 r][w = li] += E (cfac . share) over the wave's tiles
             //      in ascending order.  Between groups the sums wait in the wave's own part of the LDS area they are handed over in.
             load_e(gi);
-            load_cf(gi);
+            double cfv[NTT][4];
+            load_cf(gi, cfv);
             jx_ro_v4d macc[JX_CT_NDT];
 #pragma unroll
             for (int dt = 0; dt < JX_CT_NDT; ++dt)
@@ -489,7 +497,7 @@ jx_ordrow_kernel(JxRowOp g) {
 typedef float jx_ro_v4f __attribute__((ext_vector_type(4)));
 
 struct JxRowOp32 {
-    const float* Wfk;              // JxRowOp::Wfk, Opk, Typ rounded to fp32 (a nonzero entry below FLT_MIN in magnitude: 0), same layouts
+    const float* Wfk;              // JxRowOp::Wfk, Opk, Typ rounded to fp32 (a nonzero entry below FLT_MIN in magnitude: 0), same layouts: Wfk and Opk tile-major, [..][NXT][64][4]
     const float* Opk;
     const float* Typ;
     double T;                      // range guard: |pp| beyond it (or not finite) rejects the walker
@@ -582,29 +590,24 @@ jx_ordrow32_kernel(JxRowOp g, JxRowOp32 h) {
 #ifdef __HIP_DEVICE_COMPILE__
         if (CT) asm volatile("" : "+v"(lane_g));
 #endif
-        float bpv[NTT][4], bqv[NTT][4];
+        jx_ro_v4f bpv[NTT], bqv[NTT];                            // (tile-major, jxt::row_tile_major: one 16-byte load per lane, ordinate tile and output tile)
 #pragma unroll
         for (int tt = 0; tt < NTT; ++tt) {
             const int t = min(wv + 4 * tt, NXT - 1);
-            const float* __restrict__ ob = h.Opk + ((size_t)gi * g.nS * 256 + lane_g) * NXT + t;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bpv[tt][e] = ob[((size_t)p * 4 + e) * 64 * NXT];
-                bqv[tt][e] = ob[((size_t)(hasq ? q : p) * 4 + e) * 64 * NXT];
-            }
+            const float* __restrict__ ob = h.Opk + (((size_t)gi * g.nS * NXT + t) * 64 + lane_g) * 4;
+            bpv[tt] = *reinterpret_cast<const jx_ro_v4f*>(ob + (size_t)p * NXT * 256);
+            bqv[tt] = *reinterpret_cast<const jx_ro_v4f*>(ob + (size_t)(hasq ? q : p) * NXT * 256);
         }
         double bv[NTT][4];
         const bool fold = p < g.nfold;
         jx_ro_v4f af = jx_ro_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-        float bfv[NTT][4];
+        jx_ro_v4f bfv[NTT];
         if (fold) {
             af = round_a(load_a(g.s0f + p));
 #pragma unroll
             for (int tt = 0; tt < NTT; ++tt) {
                 const int t = min(wv + 4 * tt, NXT - 1);
-                const float* __restrict__ ob = h.Wfk + ((((size_t)gi * g.nfold + p) * 4) * 64 + lane_g) * NXT + t;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bfv[tt][e] = ob[(size_t)e * 64 * NXT];
+                bfv[tt] = *reinterpret_cast<const jx_ro_v4f*>(h.Wfk + ((((size_t)gi * g.nfold + p) * NXT + t) * 64 + lane_g) * 4);
             }
         }
         double* __restrict__ Pb = g.P + (((size_t)wt * g.npair + p) * g.ng + gi) * (size_t)(256 * NXT);
@@ -624,9 +627,9 @@ jx_ordrow32_kernel(JxRowOp g, JxRowOp32 h) {
                     for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(bfv[tt][e], af[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], bfv[tt][e], c1, 0, 0, 0);
                     for (int sf = p + g.npair; sf < g.nfold; sf += g.npair) {        // (more macro steps than pairs: short grids only)
                         const jx_ro_v4f a2 = round_a(load_a(g.s0f + sf));
-                        const float* __restrict__ ob = h.Wfk + ((((size_t)gi * g.nfold + sf) * 4) * 64 + lane_g) * NXT + t;
+                        const jx_ro_v4f b2 = *reinterpret_cast<const jx_ro_v4f*>(h.Wfk + ((((size_t)gi * g.nfold + sf) * NXT + t) * 64 + lane_g) * 4);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(ob[(size_t)e * 64 * NXT], a2[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(a2[e], ob[(size_t)e * 64 * NXT], c1, 0, 0, 0);
+                        for (int e = 0; e < 4; ++e) c1 = CT ? __builtin_amdgcn_mfma_f32_16x16x4f32(b2[e], a2[e], c1, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x4f32(a2[e], b2[e], c1, 0, 0, 0);
                     }
                 }
                 // fp64 from here on.  Plain: D[walker 4 lk + r][output li]; transposed: D[output 4 lk + r][walker li]

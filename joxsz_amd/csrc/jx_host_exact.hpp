@@ -11,7 +11,8 @@ struct ExactBuild {
     bool ok = false;
     int Nk = 0, Nkp = 0, nxt = 0, ng = 0, ng_use = 0, npair = 0, nSj = 0, nfold = 0;
     bool lean = true;
-    std::vector<double> Wfk, Typ, Opk;
+    std::vector<double> Wfk, Typ, Opk;                           // Wfk, Opk (and their fp32 roundings): tile-major, as the pair-wise kernels read them (jxt::row_tile_major)
+    std::vector<double> OpkLane;                                 // JOXSZ_X_PAIRWISE=0 only: the row operator in exact_row_layout's own order, a lane's tiles contiguous (jx_rowop_tail_kernel)
     // fp32 products (jx_config.dtype 3): the same three tables rounded once to fp32, and the range guard T = 2^t_log2 on the profile
     bool f32x = false;
     std::vector<float> Wfk32, Typ32, Opk32;
@@ -53,6 +54,19 @@ static void plan_exact(jx_ctx* ctx, const PlanShared& sh, const std::vector<doub
         xb.t_log2 = jxt::f32_range_guard_log2(jxt::ordinate_layout_abs_rowsum(xb.Typ32, nS, xb.nSj), jxt::row_layout_abs_rowsum(xb.Opk32, nS, xb.nxt, xb.ng),
                                               xb.nfold ? jxt::row_layout_abs_rowsum(xb.Wfk32, xb.nfold, xb.nxt, xb.ng) : 0.0);
     }
+    {   // the pair-wise kernels multiply one output tile at a time: their row and fold operators go tile-major, [g][s][NXT][64][4], one vector
+        // load per lane, ordinate tile and output tile (a pure permutation, behind the rounding and the guard, which read exact_row_layout's order)
+        const int nS = xb.Nkp / 16;
+        if (!ctx->exact.pairwise) xb.OpkLane = xb.Opk;
+        std::vector<double> td;
+        std::vector<float> tf;
+        jxt::row_tile_major(xb.Opk, nS, xb.nxt, xb.ng, td); xb.Opk.swap(td);
+        if (xb.nfold) { jxt::row_tile_major(xb.Wfk, xb.nfold, xb.nxt, xb.ng, td); xb.Wfk.swap(td); }
+        if (xb.f32x) {
+            jxt::row_tile_major(xb.Opk32, nS, xb.nxt, xb.ng, tf); xb.Opk32.swap(tf);
+            if (xb.nfold) { jxt::row_tile_major(xb.Wfk32, xb.nfold, xb.nxt, xb.ng, tf); xb.Wfk32.swap(tf); }
+        }
+    }
     xb.ok = true;
 }
 
@@ -85,7 +99,9 @@ static int exact_setup(jx_ctx* ctx, const ExactBuild& xb, long long tW) {
     } else {
         if (xb.nfold && (rc = dev_put_l(ctx, m.allocs, xb.Wfk.data(), xb.Wfk.size(), &m.Wfk))) return rc;
         if ((rc = dev_put_l(ctx, m.allocs, xb.Typ.data(), xb.Typ.size(), &m.Typ))) return rc;
-        if ((rc = dev_put_l(ctx, m.allocs, xb.Opk.data(), xb.Opk.size(), &m.Opk))) return rc;
+        // (the reference kernel's launches form no row product in jx_ordrow_kernel, ng = 0: the one table they read is the lane-major one)
+        const std::vector<double>& opk = m.pairwise ? xb.Opk : xb.OpkLane;
+        if ((rc = dev_put_l(ctx, m.allocs, opk.data(), opk.size(), &m.Opk))) return rc;
     }
     if ((rc = dev_new_l(ctx, m.allocs, (size_t)tW * m.Nkp, &m.y, true))) return rc;
     if ((rc = dev_new_l(ctx, m.allocs, (size_t)(tW / 16) * m.npair * m.ng * 256 * m.nxt, &m.P, true))) return rc;

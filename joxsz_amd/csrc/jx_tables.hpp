@@ -1054,6 +1054,20 @@ inline void exact_fold_layout(const std::vector<double>& Wy, int nrow, const std
     exact_row_layout(Wf, nrow, K, nSf, NXT, ng, Wfk);
 }
 
+// The row or fold operator as the pair-wise kernels read it (jx_ordrow_kernel, jx_ordrow32_kernel): a wave multiplies ONE output tile t at a
+// time, so the tile moves outside the lane and the four sub-steps inside it -- one vector load per lane, ordinate tile and output tile, a
+// wave's load one contiguous run, like Typ and Eop.  A pure permutation of exact_row_layout's / exact_fold_layout's table (or of its fp32
+// rounding), [g][s][4 e][64 lanes][NXT] -> [g][s][NXT][64 lanes][4 e]:
+//     out[((((g nS + s) NXT + t) 64 + lane) 4 + e] = in[((((g nS + s) 4 + e) 64 + lane) NXT + t]
+template <class T>
+inline void row_tile_major(const std::vector<T>& in, int nS, int NXT, int ng, std::vector<T>& out) {
+    out.resize((size_t)ng * nS * 4 * 64 * NXT);
+    for (size_t gs = 0; gs < (size_t)ng * nS; ++gs)
+        for (int t = 0; t < NXT; ++t)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 4; ++e) out[((gs * NXT + t) * 64 + lane) * 4 + e] = in[((gs * 4 + e) * 64 + lane) * NXT + t];
+}
+
 // B operand of the ordinate product (jx_ordrow_kernel): y_k = sum_j y_scale A[k][j] pp_j (joxsz_funcs.py:457-459), macro step s (16
 // radii) x column tile t (16 ordinates) x lane (lk, li) x sub-step e,   Typ[((s nS + t) 64 + 16 lk + li) 4 + e] = y_scale A[16 t + li][16 s + 4 lk + e]
 // (zero beyond the grid; A is upper triangular, so tile t has entries from step s = t on).

@@ -220,6 +220,31 @@ int jxt_exact_fold_layout(const double* Wy, int nrow, const double* r, int N, do
     std::copy(o.begin(), o.end(), out);
     return 0;
 }
+// a table in the row operator's layout [ng][nS][4][64][NXT] as the pair-wise kernels read it, [ng][nS][NXT][64][4] (jxt::row_tile_major);
+// f32 = 0: in and out are doubles, 1: floats
+int jxt_row_tile_major(const void* in, int nS, int NXT, int ng, int f32, void* out) {
+    const size_t n = (size_t)ng * nS * 256 * NXT;
+    if (f32) {
+        std::vector<float> o;
+        jxt::row_tile_major(std::vector<float>((const float*)in, (const float*)in + n), nS, NXT, ng, o);
+        std::copy(o.begin(), o.end(), (float*)out);
+    } else {
+        std::vector<double> o;
+        jxt::row_tile_major(std::vector<double>((const double*)in, (const double*)in + n), nS, NXT, ng, o);
+        std::copy(o.begin(), o.end(), (double*)out);
+    }
+    return 0;
+}
+// the fp32 rounding of a table and the largest absolute row sum of one in the row operator's layout: what the f32x range guard is derived from
+int jxt_round_to_f32(const double* in, long long n, float* out) {
+    std::vector<float> o;
+    jxt::round_to_f32(std::vector<double>(in, in + n), o);
+    std::copy(o.begin(), o.end(), out);
+    return 0;
+}
+double jxt_row_layout_abs_rowsum(const float* Opk, int nS, int NXT, int ng) {
+    return jxt::row_layout_abs_rowsum(std::vector<float>(Opk, Opk + (size_t)ng * nS * 256 * NXT), nS, NXT, ng);
+}
 int jxt_abel_ordinate_layout(const double* r, int n, double y_scale, int nS, int nSj, double* out) {
     std::vector<double> o;
     jxt::abel_ordinate_layout(std::vector<double>(r, r + n), y_scale, nS, nSj, o);

@@ -403,7 +403,9 @@ class HipContext:
         """Test hook: copy of a work buffer of the contracted route (``jx_debug_workspace``), holding the last evaluated
         chunk: 'y_map' [chunk, NU, ld] quadrant of the Compton-y map (after a y_2d tap), 'splines' [N, tW, 2] walker-minor
         (y_k, M_k), 'stage1' [NU, R, tW] rows kept per map column, 'partials' [ksplit, tW, ldx] partial rows; the constant
-        operators 'stage1_op' [1, wld, cld] (C[u][j]) and 'product_op' [K, 16, ntile] (Op[kappa][x & 15][x >> 4])."""
+        operators 'stage1_op' [1, wld, cld] (C[u][j]) and 'product_op' [K, 16, ntile] (Op[kappa][x & 15][x >> 4]).  Exact form:
+        'ordinates' [1, tW, Nkp] and 'row_op' [ng nS nxt, 64, 4], the row operator as the pair-wise kernels read it, tile-major:
+        row (g nS + s) nxt + t holds Wy[16 (g nxt + t) + (lane & 15)][16 s + 4 (lane >> 4) + e] at [lane][e]."""
         ids = {'y_map': 0, 'splines': 1, 'stage1': 2, 'partials': 3, 'stage1_op': 4, 'product_op': 5, 'ordinates': 6, 'row_op': 7}
         ptr = ctypes.c_void_p()
         geom = (ctypes.c_int32 * 4)()
